@@ -16,7 +16,10 @@ there is no host synchronisation per step.  Sequences shard across GPUs with no 
 per-GPU work is fixed); the per-frame nav records go to rank 0 over RCCL on a side stream, double buffered, off the timed
 critical path.
 
-On the line (rank 0):
+A plain run sets up, warms up, times the `--steps` steps and prints the line (`ms_per_step` = one timed step); `--dump-outputs DIR`
+writes what the last timed step computed (dump_outputs).  Everything else below is measured with `--full` only.
+
+On the line (rank 0, --full):
   roofline         the kernel group with the most time (HIP events on the stream it runs on, over the timed region): the bytes
                    one launch cannot avoid moving (DESIGN.md section 3) / mean launch duration against 8 TB/s = `frac`;
                    `frac_survey_formula` where SURVEY 8(d)'s per-unit figure counts more; `traffic` / `frac_on_traffic` from the
@@ -694,6 +697,50 @@ def host_surface(params, frames, w, h):
     return out
 
 
+DUMP_LIMIT = 60 * 10 ** 6   # bytes of the --dump-outputs arrays together (64 MB at most with the .npy headers)
+DUMP_KEYLINE_SEQS = 8       # sequences of the batch whose KeyLines --dump-outputs writes (a fixed, seeded sample)
+
+
+def dump_outputs(out_dir, ehs, slot, nav=True):
+    """--dump-outputs: what the last timed step computed, as a caller of the path receives it, one float64 .npy per field in `out_dir`:
+      nav_<field>       [sequences, ...]  every sequence's nav record (edgehip_read_nav); --config stage_a: kn [sequences] instead
+      keylines_<field>  [KeyLines, ...]   the KeyLines of slot `slot` (None: the current one) of DUMP_KEYLINE_SEQS sequences drawn with
+                                          a fixed seed, one after the other (edgehip_download_keylines_batch)
+      keylines_sequence [KeyLines]        the sequence each of those KeyLines belongs to
+    The sample stops before the files would pass DUMP_LIMIT.  Called after the timed region, before anything else runs a step."""
+    from rebvo_amd import edgehip
+    os.makedirs(out_dir, exist_ok=True)
+    B = ehs[0].nseq
+    n = B * len(ehs)
+    arrays = {}
+    if nav:
+        recs = [r for e in ehs for r in e.read_nav()]
+        for f in [f for f, _ in edgehip.Nav._fields_ if hasattr(recs[0], f)]:   # (the stub device's records carry a few of them)
+            arrays["nav_" + f] = np.array([v[:] if hasattr(v, "_length_") else v for v in (getattr(r, f) for r in recs)], np.float64)
+    else:
+        arrays["kn"] = np.array([v for e in ehs for v in e.get_kn(slot)], dtype=np.float64)
+    if hasattr(ehs[0], "download_keylines_batch"):
+        fields = [f for f in edgehip.KEYLINE_DTYPE.names if not f.startswith("_")]
+        per_kl = 8 * (1 + sum(int(np.prod(edgehip.KEYLINE_DTYPE[f].shape)) for f in fields))
+        left = DUMP_LIMIT - sum(a.nbytes for a in arrays.values())
+        sample = sorted(int(s) for s in np.random.default_rng(0).choice(n, size=min(DUMP_KEYLINE_SEQS, n), replace=False))
+        kls, seq_of = [], []
+        for s in sample:
+            e = ehs[s // B]
+            kl = e.download_keylines_batch(e.cur_slot() if slot is None else slot, [s % B])[0]
+            if len(kl) * per_kl > left:
+                break
+            left -= len(kl) * per_kl
+            kls.append(kl)
+            seq_of.append(np.full(len(kl), s, np.float64))
+        kl = np.concatenate(kls) if kls else np.zeros(0, edgehip.KEYLINE_DTYPE)
+        arrays["keylines_sequence"] = np.concatenate(seq_of) if seq_of else np.zeros(0)
+        for f in fields:
+            arrays["keylines_" + f] = kl[f].astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 LINE_LIMIT = 4096      # bytes of the one JSON line (the driver reads it out of a bounded stdout tail: round 4's 22 KB line did not parse)
 EXTRAS_FILE = "bench_extras.json"
 
@@ -982,9 +1029,9 @@ def other_configs(args):
                         ("tracker_f32", ["--tracker-f32", "--cpu-frames", cf, "--cpu-procs", "0"])):
         try:
             t_sub = time.perf_counter()
-            js = run(["--no-extras", "--steps", "20", "--warmup", "5", "--nseq", str(args.nseq)] + flags, 420)
+            js = run(["--full", "--no-extras", "--steps", "20", "--warmup", "5", "--nseq", str(args.nseq)] + flags, 420)
             extras[name] = js
-            extras[name]["command"] = "python bench.py --no-extras --steps 20 --warmup 5 " + " ".join(flags)
+            extras[name]["command"] = "python bench.py --full --no-extras --steps 20 --warmup 5 " + " ".join(flags)
             extras[name]["wall_s"] = round(time.perf_counter() - t_sub, 1)
         except Exception as e:
             extras[name] = {"value": None, "error": f"{type(e).__name__}: {e}"[:300]}
@@ -993,7 +1040,7 @@ def other_configs(args):
     try:
         best = None
         for _ in range(3):
-            js = run(["--no-extras", "--imu", "--nseq", "1", "--steps", "200", "--warmup", "12", "--cpu-frames", "0"], 300)
+            js = run(["--full", "--no-extras", "--imu", "--nseq", "1", "--steps", "200", "--warmup", "12", "--cpu-frames", "0"], 300)
             best = js["ms_per_step"] if best is None else min(best, js["ms_per_step"])
         if isinstance(extras.get("imu"), dict):
             extras["imu"]["single_sequence_ms_per_frame"] = best
@@ -1112,7 +1159,18 @@ def main():
     ap.add_argument("--no-live-pmc", action="store_true",
                     help="do not run the two rocprofv3 counter passes of this command (N = 1 only) that make roofline.traffic an observation of "
                          "this run; the committed counters of profiles/pmc_latest.json are used instead, under their source stamp")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline as well: the HIP-event profile and roofline of every kernel group "
+                         "(with the live rocprofv3 counter passes), the CPU baseline and the pose check against the CPU reference, the "
+                         "small-batch sweep and the plugin-surface legs.  Off by default: a plain run sets up, warms up, times the steps "
+                         "and prints the line.  --extras implies it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed, as a caller of the path receives it, to DIR/<name>.npy "
+                         "(float64): every sequence's nav record field by field (nav_*) and the KeyLines of a fixed, seeded sample of "
+                         "sequences (keylines_*); --config stage_a: the KeyLine counts (kn) and the KeyLine sample.  Same arguments, same inputs")
     args = ap.parse_args()
+    if args.extras:
+        args.full = True
     user_no_extras = bool(args.no_extras)   # (--imu / --tracker-f32 switch the extras off further down: the counter passes go by what was asked for)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -1193,8 +1251,8 @@ def main():
     radius = params.search_range
     C = max(1, args.contexts)
     B, K, Wm = args.nseq // C, args.steps, args.warmup   # B = sequences per context
-    # every rank checks a sample of its own sequences against the CPU reference (pose RMSE); rank 0 also times the reference
-    cpu_any = args.cpu_frames > 0
+    # --full: every rank checks a sample of its own sequences against the CPU reference (pose RMSE); rank 0 also times the reference
+    cpu_any = args.full and args.cpu_frames > 0
     cpu_legs = cpu_any and not args.imu
     cpu_legs_imu = cpu_any and args.imu and rank == 0 and world == 1
     if args.imu:
@@ -1300,8 +1358,9 @@ def main():
         for k in range(Wm):
             stage_a_step(k)
         rp.sync()
-        eh.profile_enable(True)
-        eh.profile_select(None)
+        if args.full:   # HIP events on every stage-A kernel group: the roofline and the per-kernel times
+            eh.profile_enable(True)
+            eh.profile_select(None)
         # ---- timed region (stage A only): EXACTLY K steps between barriers ----
         if world > 1:
             dist.barrier()
@@ -1314,7 +1373,9 @@ def main():
             dist.barrier()
         dt = time.perf_counter() - t0
         # ---- end of timed region ----
-        prof = {g: (ms, calls) for g, (ms, calls) in eh.profile_read().items() if calls}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"), ehs, (Wm + K - 1) % 3, nav=False)
+        prof = {g: (ms, calls) for g, (ms, calls) in eh.profile_read().items() if calls} if args.full else {}
         kn_mean = float(np.mean([v for e in ehs for v in e.get_kn((Wm + K - 1) % 3)]))
         if world > 1:
             tmax = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
@@ -1323,9 +1384,15 @@ def main():
         if rank == 0:
             fbytes = 3 * n_px + 4 * n_px + 168 * kn_mean       # stage A
             fps = B * C * world * K / dt
-            dom = max(prof, key=lambda g: prof[g][0])
-            per_launch = prof[dom][0] * 1e-3 / prof[dom][1]
-            ab = algorithmic_bytes(dom, kn_mean, n_px, radius, B)
+            roof = None
+            if prof:   # --full
+                dom = max(prof, key=lambda g: prof[g][0])
+                per_launch = prof[dom][0] * 1e-3 / prof[dom][1]
+                ab = algorithmic_bytes(dom, kn_mean, n_px, radius, B)
+                roof = {"bound": "hbm", "kernel": dom, "achieved": round(ab / per_launch / 1e9, 2), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(ab / per_launch / 1e9 / HBM_PEAK_GBS, 5), "traffic": None,
+                        "launch_us": round(per_launch * 1e6, 2), "algorithmic_bytes_per_launch": int(ab),
+                        "launches_timed": prof[dom][1]}
             cpu = None
             if cpu_legs:
                 from oracle import oracle
@@ -1340,7 +1407,7 @@ def main():
                        "sample": f"{len(ts)} frames of stage A (sspace::build + edge_finder::detect) on 1 core of {_usable_cores()} "
                                  f"({_cpu_model()})", "ms_per_frame": round(float(ts.mean()) * 1e3, 3),
                        "median_ms": round(float(np.median(ts)) * 1e3, 3), "p95_ms": round(float(np.percentile(ts, 95)) * 1e3, 3)}
-            print(json.dumps({
+            line = {
                 "metric": "HBM GB/s (DoG + edge_finder KeyLine extraction) 752x480", "value": round(fbytes * fps / world / 1e9, 2),
                 "unit": "GB/s", "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": round(dt / K * 1e3, 4),
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32 scale space / f64 plane fit",
@@ -1350,13 +1417,12 @@ def main():
                                        "SURVEY 8(d) stage-A bytes (3N + 4N + 168 kn) x frames/s per GPU",
                            "sequences_per_gpu": B * C, "frames_per_step": B * C * world, "keylines_per_frame": round(kn_mean, 1),
                            "frames_per_s": round(fps, 1), "algorithmic_MB_per_frame": round(fbytes / 1e6, 3)},
-                "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(ab / per_launch / 1e9, 2), "peak": HBM_PEAK_GBS,
-                             "unit": "GB/s", "frac": round(ab / per_launch / 1e9 / HBM_PEAK_GBS, 5), "traffic": None,
-                             "launch_us": round(per_launch * 1e6, 2), "algorithmic_bytes_per_launch": int(ab),
-                             "launches_timed": prof[dom][1]},
+                "roofline": roof,
                 "stage_a_hbm_frac": round(fbytes * fps / world / 1e9 / HBM_PEAK_GBS, 5),
-                "cpu_baseline": cpu,
-                "kernel_us_per_step": {g: round(ms / K * 1e3, 1) for g, (ms, calls) in prof.items()}}))
+                "cpu_baseline": cpu}
+            if prof:
+                line["kernel_us_per_step"] = {g: round(ms / K * 1e3, 1) for g, (ms, calls) in prof.items()}
+            print(json.dumps(line))
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
@@ -1372,20 +1438,21 @@ def main():
         if dist_on:
             dist.barrier()
 
-    # ---- warmup (also finds the dominant kernel group with the built-in HIP-event profiler) ----
-    prof_steps = min(4, max(1, Wm // 4))
+    # ---- warmup (--full: also finds the dominant kernel group with the built-in HIP-event profiler) ----
+    prof_steps = min(4, max(1, Wm // 4)) if args.full else 0
     for k in range(Wm - prof_steps):
         rp.step(k)
-    rp.sync()
-    eh.profile_enable(True)
-    eh.profile_select(None)
-    for k in range(Wm - prof_steps, Wm):
-        rp.step(k)
-    prof = eh.profile_read()
-    eh.profile_enable(False)
-    groups = {g: (ms, calls) for g, (ms, calls) in prof.items() if calls}
-    dominant = max(groups, key=lambda g: groups[g][0]) if groups else None
-    breakdown = {g: round(ms / prof_steps * 1e3, 1) for g, (ms, calls) in groups.items()}  # us per step
+    dominant = breakdown = None
+    if prof_steps:
+        rp.sync()
+        eh.profile_enable(True)
+        eh.profile_select(None)
+        for k in range(Wm - prof_steps, Wm):
+            rp.step(k)
+        prof = eh.profile_read()
+        eh.profile_enable(False)
+        groups = {g: (ms, calls) for g, (ms, calls) in prof.items() if calls}
+        dominant = max(groups, key=lambda g: groups[g][0]) if groups else None
 
     # ---- timed region: EXACTLY K steps between barriers ----
     if dominant and not args.no_roofline_events:
@@ -1461,6 +1528,8 @@ def main():
         log0 = eh.read_nav_log_array(Wm, K)
         gpu_traj = {s: [(log0[k, s]["Pos"].copy(), log0[k, s]["Pose"].reshape(3, 3).copy(), log0[k, s]["Vel"].copy(),
                          log0[k, s]["RotLie"].copy()) for k in range(K)] for s in check_seqs}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"), ehs, None)
     last = [n for e in ehs for n in e.read_nav()]
     kn_mean = float(np.mean([n.kn for n in last]))
     kn_timed = float(np.mean((log_all[Wm:] if log_all is not None else eh.read_nav_log_array(Wm, K))["kn"])) if rank == 0 else kn_mean   # over every timed frame, context 0
@@ -1556,75 +1625,78 @@ def main():
         return
 
     value = B * C * world * K / dt
-    # ---- per-kernel attribution: four more steps (frames right behind the timed ones, i.e. of the same cost) with the HIP-event
-    # profiler on every group — not part of the timed region, and not the early warm-up frames whatever --warmup is ----
-    prof_steps = 4
-    eh.profile_select(None)
-    eh.profile_enable(True)
-    for k in range(Wm + K, Wm + K + prof_steps):
-        rp.step(k)
-    prof = eh.profile_read()
-    eh.profile_enable(False)
-    groups = {g: (ms, calls) for g, (ms, calls) in prof.items() if calls}
-    breakdown = {g: round(ms / prof_steps * 1e3, 1) for g, (ms, calls) in groups.items()}  # us per step
-    # ---- roofline of the dominant kernel group, and of all of them ----
-    # `frac` = compulsory bytes of what is launched / launch time / 8 TB/s; `frac_survey_formula` = the same with SURVEY 8(d)'s
-    # per-unit figure where that counts bytes a launch does not have to move; `frac_on_traffic` = the rate at which the kernel
-    # really moves bytes (committed PMC passes — used only when they were taken with THIS library's sources, else null);
-    # `issue_frac` = share of the kernel's cycles in which its SIMDs issue VALU work (committed SQ counters, same rule): a kernel
-    # priced only against a roofline it is not bound by tells nobody anything.
-    under_profiler = any("rocprof" in os.environ.get(v, "") for v in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB"))
-    if (world == 1 and not stub and not args.no_live_pmc and not user_no_extras and not os.environ.get("BENCH_LIVE_PMC_CHILD")
-            and not under_profiler and args.config == "full"):
-        child = [a for a in sys.argv[1:] if a != "--extras"] + ["--gpus", "1", "--nseq", str(B * C), "--steps", str(K), "--warmup", str(Wm),
-                                                                "--cpu-frames", "0", "--no-extras", "--no-roofline-events", "--no-live-pmc"]
-        torch.cuda.synchronize()
-        live_pmc_passes(child, B)
-    elif not LIVE_PMC["used"]:
-        LIVE_PMC["note"] = "switched off (--no-live-pmc / --no-extras / N > 1 / a profiler around this process)"
-    calib, calib_src = fetch_calibration()
-    kn_pmc = pmc_kn() or kn_mean
-    issue = issue_fracs()
+    roof, roof_all = None, {}
+    if args.full:
+        # ---- per-kernel attribution: four more steps (frames right behind the timed ones, i.e. of the same cost) with the HIP-event
+        # profiler on every group — not part of the timed region, and not the early warm-up frames whatever --warmup is ----
+        prof_steps = 4
+        eh.profile_select(None)
+        eh.profile_enable(True)
+        for k in range(Wm + K, Wm + K + prof_steps):
+            rp.step(k)
+        prof = eh.profile_read()
+        eh.profile_enable(False)
+        groups = {g: (ms, calls) for g, (ms, calls) in prof.items() if calls}
+        breakdown = {g: round(ms / prof_steps * 1e3, 1) for g, (ms, calls) in groups.items()}  # us per step
+        # ---- roofline of the dominant kernel group, and of all of them ----
+        # `frac` = compulsory bytes of what is launched / launch time / 8 TB/s; `frac_survey_formula` = the same with SURVEY 8(d)'s
+        # per-unit figure where that counts bytes a launch does not have to move; `frac_on_traffic` = the rate at which the kernel
+        # really moves bytes (committed PMC passes — used only when they were taken with THIS library's sources, else null);
+        # `issue_frac` = share of the kernel's cycles in which its SIMDs issue VALU work (committed SQ counters, same rule): a kernel
+        # priced only against a roofline it is not bound by tells nobody anything.
+        under_profiler = any("rocprof" in os.environ.get(v, "") for v in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB"))
+        if (world == 1 and not stub and not args.no_live_pmc and not user_no_extras and not os.environ.get("BENCH_LIVE_PMC_CHILD")
+                and not under_profiler and args.config == "full"):
+            argv = [a for a in sys.argv[1:] if a not in ("--extras", "--full") and not a.startswith("--dump-outputs=")]
+            if "--dump-outputs" in argv:   # (the outputs are this process's to write)
+                del argv[argv.index("--dump-outputs"):argv.index("--dump-outputs") + 2]
+            child = argv + ["--full", "--gpus", "1", "--nseq", str(B * C), "--steps", str(K), "--warmup", str(Wm), "--cpu-frames", "0",
+                            "--no-extras", "--no-roofline-events", "--no-live-pmc"]
+            torch.cuda.synchronize()
+            live_pmc_passes(child, B)
+        elif not LIVE_PMC["used"]:
+            LIVE_PMC["note"] = "switched off (--no-live-pmc / --no-extras / N > 1 / a profiler around this process)"
+        calib, calib_src = fetch_calibration()
+        kn_pmc = pmc_kn() or kn_mean
+        issue = issue_fracs()
 
-    def roof_of(g, ms, calls, kn):
-        ab = algorithmic_bytes(g, kn, n_px, radius, B)
-        if not ab or not calls:
-            return None
-        per = ms * 1e-3 / calls
-        r_ = {"launch_us": round(per * 1e6, 1), "achieved_GBs": round(ab / per / 1e9, 1), "frac": round(ab / per / 1e9 / HBM_PEAK_GBS, 4),
-              "algorithmic_bytes_per_launch": int(ab)}
-        sb = survey_bytes(g, kn, n_px, radius, B)
-        if sb != ab:
-            r_["frac_survey_formula"] = round(sb / per / 1e9 / HBM_PEAK_GBS, 4)
-        tr, _ = calibrated_traffic(g, B, kn_pmc, calib)
-        ab_pmc = algorithmic_bytes(g, kn_pmc, n_px, radius, B)
-        if tr and ab_pmc:   # counters taken at another KeyLine count: the ratio to the algorithmic bytes there, applied here
-            r_["traffic"] = int(tr / ab_pmc * ab)
-            r_["frac_on_traffic"] = round(tr / ab_pmc * ab / per / 1e9 / HBM_PEAK_GBS, 4)
-        if g in issue and not (f32 and not LIVE_PMC.get("issue") and g.startswith("B.try_velrot")):   # (the committed SQ passes are the fp64 kernels')
-            r_["issue_frac"] = issue[g]
-        return r_
-    roof = None
-    if dominant and dom_calls:
-        # bytes of THESE launches / time of THESE launches: the KeyLine count of the timed frames (kn_timed)
-        rd = roof_of(dominant, dom_ms, dom_calls, kn_timed)
-        if rd:
-            roof = {"bound": "hbm", "kernel": dominant, "achieved": rd["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": rd["frac"], "frac_on_traffic": rd.get("frac_on_traffic"), "traffic": rd.get("traffic"),
-                    "launch_us": rd["launch_us"], "algorithmic_bytes_per_launch": rd["algorithmic_bytes_per_launch"],
-                    "launches_timed": dom_calls, "issue_frac": rd.get("issue_frac")}
-            if "frac_survey_formula" in rd:
-                roof["frac_survey_formula"] = rd["frac_survey_formula"]
-            roof["traffic_live"] = bool(LIVE_PMC["used"]) and roof["traffic"] is not None
-            roof["issue_live"] = bool(LIVE_PMC.get("issue")) and roof.get("issue_frac") is not None
-            if roof["traffic"] is None:
-                roof["traffic_note"] = pmc_stamp_note()
-    roof_all = {}
-    for g, (ms, calls) in groups.items():
-        rg = roof_of(g, ms, calls, kn_mean)
-        if rg:
-            rg["launches_per_step"] = calls // prof_steps
-            roof_all[g] = rg
+        def roof_of(g, ms, calls, kn):
+            ab = algorithmic_bytes(g, kn, n_px, radius, B)
+            if not ab or not calls:
+                return None
+            per = ms * 1e-3 / calls
+            r_ = {"launch_us": round(per * 1e6, 1), "achieved_GBs": round(ab / per / 1e9, 1), "frac": round(ab / per / 1e9 / HBM_PEAK_GBS, 4),
+                  "algorithmic_bytes_per_launch": int(ab)}
+            sb = survey_bytes(g, kn, n_px, radius, B)
+            if sb != ab:
+                r_["frac_survey_formula"] = round(sb / per / 1e9 / HBM_PEAK_GBS, 4)
+            tr, _ = calibrated_traffic(g, B, kn_pmc, calib)
+            ab_pmc = algorithmic_bytes(g, kn_pmc, n_px, radius, B)
+            if tr and ab_pmc:   # counters taken at another KeyLine count: the ratio to the algorithmic bytes there, applied here
+                r_["traffic"] = int(tr / ab_pmc * ab)
+                r_["frac_on_traffic"] = round(tr / ab_pmc * ab / per / 1e9 / HBM_PEAK_GBS, 4)
+            if g in issue and not (f32 and not LIVE_PMC.get("issue") and g.startswith("B.try_velrot")):   # (the committed SQ passes are the fp64 kernels')
+                r_["issue_frac"] = issue[g]
+            return r_
+        if dominant and dom_calls:
+            # bytes of THESE launches / time of THESE launches: the KeyLine count of the timed frames (kn_timed)
+            rd = roof_of(dominant, dom_ms, dom_calls, kn_timed)
+            if rd:
+                roof = {"bound": "hbm", "kernel": dominant, "achieved": rd["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": rd["frac"], "frac_on_traffic": rd.get("frac_on_traffic"), "traffic": rd.get("traffic"),
+                        "launch_us": rd["launch_us"], "algorithmic_bytes_per_launch": rd["algorithmic_bytes_per_launch"],
+                        "launches_timed": dom_calls, "issue_frac": rd.get("issue_frac")}
+                if "frac_survey_formula" in rd:
+                    roof["frac_survey_formula"] = rd["frac_survey_formula"]
+                roof["traffic_live"] = bool(LIVE_PMC["used"]) and roof["traffic"] is not None
+                roof["issue_live"] = bool(LIVE_PMC.get("issue")) and roof.get("issue_frac") is not None
+                if roof["traffic"] is None:
+                    roof["traffic_note"] = pmc_stamp_note()
+        for g, (ms, calls) in groups.items():
+            rg = roof_of(g, ms, calls, kn_mean)
+            if rg:
+                rg["launches_per_step"] = calls // prof_steps
+                roof_all[g] = rg
     # whole-frame algorithmic bytes, SURVEY.md §8(d) formulas with the measured kn and evaluation count
     r = radius
     frame_bytes = (3 * n_px + 4 * n_px + 168 * kn_mean) + (8 * n_px + 8 * 2 * r * kn_mean + evals * 84 * kn_mean) + \
@@ -1748,9 +1820,9 @@ def main():
             cpu = cpu or {"value": None}
             cpu["error"] = f"{type(e).__name__}: {e}"[:300]
 
-    # ---- the other batch shapes (N = 1, after the timed region) ----
+    # ---- the other batch shapes (--full, N = 1, after the timed region) ----
     sweep = hetero = None
-    if world == 1 and not args.no_extras and not args.imu:
+    if world == 1 and args.full and not args.no_extras and not args.imu:
         sweep = []
         for n in (1, 8, 64):
             o = np.arange(n, dtype=np.int64) % (2 * (args.pool - 1))
@@ -1761,7 +1833,7 @@ def main():
             r2.close()
         sweep.append({"sequences_per_launch": B, "frames_per_s": round(value, 1), "ms_per_step": round(dt / K * 1e3, 4)})
     surface = None
-    if world == 1 and not args.no_extras and not args.imu and args.config == "full" and not tum:
+    if world == 1 and args.full and not args.no_extras and not args.imu and args.config == "full" and not tum:
         try:
             surface = host_surface(params, frames, w, h)
         except Exception as e:
@@ -1884,18 +1956,22 @@ def main():
                    "tryvelrot_evals_per_frame": evals, "estimation_ok": f"{ok}/{B * C}",
                    "algorithmic_MB_per_frame": round(frame_bytes / 1e6, 2),
                    "whole_path_hbm_frac": round(frame_bytes * value / world / 1e9 / HBM_PEAK_GBS, 5)},
-        "roofline": roof, "cpu_baseline": cpu, "pose_rmse": pose, "kernel_us_per_step": breakdown,
-        "kernel_us_per_step_source": "HIP events of the 4 steps that follow the timed region (profiler on every kernel group; the timed "
-                                     "region itself carries events on the dominant group only)",
-        "roofline_kernels": roof_all,
+        "roofline": roof, "cpu_baseline": cpu, "pose_rmse": pose,
         # no SCALE record of this repository exists (the driver's 8-GPU node has not been available): N > 1 is covered by the gloo
         # tests and a 2-rank dry run, not by a measured curve
         "scaling_measured": False,
-        "traffic_source": ("live: " + LIVE_PMC["note"] + f" ({LIVE_PMC.get('seconds')} s, {LIVE_PMC.get('kernels')} kernels)") if LIVE_PMC["used"] else
-                          (PMC_FILE + " (rocprofv3 --pmc passes of this command, committed; used only when stamped with the sources of "
-                                      "the library that is running: " + pmc_stamp_note() + "); live passes: " + LIVE_PMC["note"]),
-        "traffic_calibration": {"factors_true_over_reported": {k: round(v, 3) for k, v in calib.items()}, "source": calib_src},
     }
+    if args.full:
+        full.update({
+            "kernel_us_per_step": breakdown,
+            "kernel_us_per_step_source": "HIP events of the 4 steps that follow the timed region (profiler on every kernel group; the timed "
+                                         "region itself carries events on the dominant group only)",
+            "roofline_kernels": roof_all,
+            "traffic_source": ("live: " + LIVE_PMC["note"] + f" ({LIVE_PMC.get('seconds')} s, {LIVE_PMC.get('kernels')} kernels)") if LIVE_PMC["used"] else
+                              (PMC_FILE + " (rocprofv3 --pmc passes of this command, committed; used only when stamped with the sources of "
+                                          "the library that is running: " + pmc_stamp_note() + "); live passes: " + LIVE_PMC["note"]),
+            "traffic_calibration": {"factors_true_over_reported": {k: round(v, 3) for k, v in calib.items()}, "source": calib_src},
+        })
     full["launched_by"] = "bench.py itself (no launcher around the command)" if os.environ.get("BENCH_SELF_LAUNCHED") == "1" else \
                           ("torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ else "direct")
     if f32:

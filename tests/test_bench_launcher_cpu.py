@@ -77,3 +77,20 @@ def test_device_side_records_equal_the_host_side_ones():
     seq_ids = list(range(40, 40 + B))
     got = shard.nav_records_device(raw, 3, seq_ids).numpy()
     assert np.array_equal(got, shard.nav_records(arr, 3, seq_ids))
+
+
+def test_dump_outputs_writes_every_ranks_last_step_as_float64(tmp_path):
+    """--dump-outputs DIR: after the timed steps every rank writes the nav records of its last timed step, one float64 .npy per field
+    (DIR/rank<r>/ when N > 1); on the stub device the records carry the frame index, so the file says which step it holds."""
+    K, W, B = 5, 3, 4
+    rc, out, err = _run(["--gpus", "2", "--nseq", str(B), "--pool", "4", "--steps", str(K), "--warmup", str(W), "--dump-outputs", str(tmp_path)],
+                        {"BENCH_STUB_DEVICE": "1", "BENCH_BACKEND": "gloo"})
+    assert rc == 0, err[-2000:]
+    line = json.loads(out.strip())
+    assert line["steps"] == K and line["ms_per_step"] > 0
+    for r in range(2):
+        frame = np.load(tmp_path / f"rank{r}" / "nav_frame.npy")
+        kn = np.load(tmp_path / f"rank{r}" / "nav_kn.npy")
+        assert frame.dtype == np.float64 and kn.dtype == np.float64 and frame.shape == (B,)
+        assert np.all(frame == W + K - 1)
+        assert np.array_equal(kn, 12000 + np.arange(B) % 7)

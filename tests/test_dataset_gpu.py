@@ -123,7 +123,7 @@ def test_bench_replays_a_mounted_dataset(tmp_path):
     w, h, n = 752, 480, 12
     frames = [f for f, _, _ in synth.billboard_sequence(w, h, n, seed=23)]
     _write_euroc_set(tmp_path / "MH_xx", frames, 1403636579763555584)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--nseq", "6", "--steps", "6", "--warmup", "4", "--no-extras", "--cpu-frames", "8",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--nseq", "6", "--steps", "6", "--warmup", "4", "--no-extras", "--cpu-frames", "8",
            "--cpu-procs", "0"]
     env = dict(os.environ, BENCH_FORCE_MOVER="0", BENCH_EXTRAS_FILE=str(tmp_path / "bench_extras.json"))
     r = subprocess.run(cmd + ["--dataset", str(tmp_path / "MH_xx")], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)

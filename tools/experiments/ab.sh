@@ -4,10 +4,8 @@
 cd "$GRAFT_REPO_ROOT"
 for v in A B A B; do
   cp tools/experiments/bin/libedgehip_$v.so rebvo_amd/lib/libedgehip.so
-  python bench.py --steps 10 --warmup 4 --no-extras --cpu-frames 0 > gpurun_out/ab_$v.json 2>gpurun_out/ab_$v.err
-  python - <<PY
-import json
-d=json.loads(open("gpurun_out/ab_$v.json").read().strip().splitlines()[-1])
-print("$v", round(d["value"]), d["ms_per_step"], {k:round(x) for k,x in d["kernel_us_per_step"].items()})
-PY
+  python bench.py --full --steps 10 --warmup 4 --no-extras --cpu-frames 0 2>/dev/null | python -c "
+import json, sys
+d = json.loads(sys.stdin.read().strip().splitlines()[-1])
+print('$v', round(d['value']), d['ms_per_step'], {k: round(x) for k, x in d['kernel_us_per_step'].items()})"
 done

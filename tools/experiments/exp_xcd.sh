@@ -1,6 +1,6 @@
 #!/bin/bash
 for X in 0 1; do
-EDGEHIP_XCD=$X python bench.py --steps 20 --warmup 12 --cpu-frames 0 | python -c "
+EDGEHIP_XCD=$X python bench.py --full --steps 20 --warmup 12 --cpu-frames 0 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d['kernel_us_per_step']

@@ -24,7 +24,7 @@ done
 cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}"
 OUT=$PWD/gpurun_out/$TAG; mkdir -p "$OUT"
 line() {   # one bench run -> value, ms per step, the named groups
-  timeout 400 python bench.py $BARGS --no-extras --cpu-frames 0 2>/dev/null | GROUPS_="$GROUPS_" python -c "
+  timeout 400 python bench.py --full $BARGS --no-extras --cpu-frames 0 2>/dev/null | GROUPS_="$GROUPS_" python -c "
 import sys, json, os
 l = sys.stdin.read(); j = json.loads(l[l.index('{'):]); k = json.load(open('bench_extras.json'))['kernel_us_per_step']
 print(j['value'], j['ms_per_step'], {g: k.get(g) for g in os.environ['GROUPS_'].split()}, j['config'].get('keylines_per_frame_timed_mean'))"

@@ -3,7 +3,7 @@
 #   STAGES="tests bench" tools/gpu_round.sh r06_a
 #   tests   pytest -m gpu                       -> pytest_gpu.log
 #   smoke   __graft_entry__.smoke()             -> smoke.log
-#   bench   the driver's command                -> bench.json (the one line), bench_extras.json, bench.err, bench_wall_s
+#   bench   the driver's command with --full    -> bench.json (the one line), bench_extras.json, bench.err, bench_wall_s
 #   extras  python bench.py --extras            -> bench_with_extras.json / bench_extras_full.json
 #   trace   rocprofv3 --kernel-trace --stats    -> kernel_stats.txt
 #   pmc     FETCH_SIZE / WRITE_SIZE passes      -> pmc.json (stamped with the library's source sha, batch size and KeyLine count)
@@ -22,7 +22,7 @@ has() { [[ " $STAGES " == *" $1 "* ]]; }
 
 if has bench; then
   T0=$(date +%s.%N)
-  timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err"
   echo "bench exit $?"
   T1=$(date +%s.%N)
   python - "$OUT" "$T0" "$T1" <<'PY'
@@ -40,7 +40,7 @@ fi
 
 if has ranks8; then
   T0=$(date +%s.%N)
-  BENCH_BACKEND=gloo BENCH_EXTRAS_FILE="$OUT/bench_8rank_gloo_extras.json" timeout 900 python3 bench.py --gpus 8 --nseq ${RANKS8_NSEQ:-128} --steps 20 --warmup 5 \
+  BENCH_BACKEND=gloo BENCH_EXTRAS_FILE="$OUT/bench_8rank_gloo_extras.json" timeout 900 python3 bench.py --full --gpus 8 --nseq ${RANKS8_NSEQ:-128} --steps 20 --warmup 5 \
       > "$OUT/bench_8rank_gloo.json" 2> "$OUT/bench_8rank_gloo.err"
   echo "ranks8 exit $? wall $(python -c "import time;print(round(time.time()-$T0,1))") s"
   head -c 3000 "$OUT/bench_8rank_gloo.json"; echo
