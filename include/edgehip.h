@@ -452,6 +452,50 @@ int edgehip_build_undistort_map(const edgehip_params *params, int32_t *inx, int3
  * device with the same integer arithmetic (what PipeBuffer::imgc holds after rebvo_first_t.cpp:231). */
 int edgehip_download_undistorted(edgehip_ctx *ctx, int seq, int slot, uint8_t *rgb24);
 
+/* ---- dense depth fill (the visualizer's depth_filler) ----------------------------------------------------------------
+ * The inverse-depth grid that depth_filler interpolates from a KeyLine list (src/visualizer/depth_filler.cpp), in the order both of
+ * the reference's callers run it — ResetData, FillEdgeData(edge_tracker&, ThreshRelRho, ThreshMatchNum, discart), InitCoarseFine,
+ * Integrate(IterNum) — the visualizer per received frame (src/visualizer/visualizer.cpp:303, 436-440) and the key-frame path per key
+ * frame (src/mtracklib/keyframe.cpp:171-184, app/kf_visualizer/main.cpp:106).  Grid gw x gh = (w / block_w) x (h / block_h), cell
+ * (x, y) at y * gw + x.  rho, s_rho and fixed equal the reference's bit for bit (fp64 throughout, the reference's order of
+ * operations; tests/depth_fill_port.py restates it) — except the sign and payload of a NaN the arithmetic creates (inf - inf,
+ * 0 * inf): the GPU's default NaN is positive, x86 SSE's negative.  NaNs a KeyLine carries in pass through unchanged.  Two departures, both where the reference has no defined result or writes
+ * through its argument:
+ *   - a KeyLine whose cell index y * gw + x lands past the grid is dropped.  (With w % block_w != 0 a KeyLine in the partial
+ *     column gets x == gw and lands in the first cell of the next row, as in the reference; on the last row the reference writes
+ *     past its buffer.)
+ *   - FillEdgeData sets kl.rho = kl.rho0 in the tracker's list for a negative rho it accepts (discard = 0); the fill only reads. */
+typedef enum edgehip_bound_mode {
+    EDGEHIP_BOUND_NONE = 0,      /* depth_filler::BOUND_NONE: every cell takes the coarse-fine / neighbour mean (both callers use this) */
+    EDGEHIP_BOUND_CORNERS = 1,   /* BOUND_CORNERS: the four corner cells keep s_rho = 2 RHO_MAX */
+    EDGEHIP_BOUND_FULL = 2       /* BOUND_FULL: every border cell keeps s_rho = 2 RHO_MAX */
+} edgehip_bound_mode;
+typedef struct edgehip_depth_fill_params {
+    int32_t block_w, block_h;    /* &DepthFiller PixelBlockSize (app/kf_visualizer/main.cpp:56; the visualizer fixes 10, visualizer.cpp:303) */
+    int32_t iter_num;            /* IterNum: Integrate1Step sweeps (main.cpp:59, visualizer.cpp:561); 0 = coarse-fine only */
+    double thresh_rel_rho;       /* ThreshRelRho: KeyLines with s_rho / rho > this are skipped (main.cpp:57, visualizer.cpp:559) */
+    int32_t thresh_match_num;    /* ThreshMatchNum: m_num below this counts as unmatched (main.cpp:58, visualizer.cpp:560) */
+    int32_t bound_mode;          /* edgehip_bound_mode (depth_filler's bound_modes) */
+    int32_t discard;             /* FillEdgeData's discart: != 0 skips unmatched KeyLines, 0 folds them with weight 1 / RHO_MAX^2 */
+} edgehip_depth_fill_params;
+/* Replaces the construction `depth_filler(cam, {bw, bh}, bound_mode)` (depth_filler.cpp:30-39) for every sequence of the context:
+ * allocates the grids and scratch (about 17 B per cell and 8 B per KeyLine of capacity, per sequence).  params == NULL frees them.
+ * EDGEHIP_ERR_ARG for a block size < 1, iter_num < 0, a grid smaller than 1x1 or an unknown bound_mode. */
+int edgehip_depth_fill_enable(edgehip_ctx *ctx, const edgehip_depth_fill_params *params);
+/* depth_filler::gridSize (depth_filler.h:95-97).  EDGEHIP_ERR_STATE if the fill is not enabled. */
+int edgehip_depth_fill_size(edgehip_ctx *ctx, int32_t *gw, int32_t *gh);
+/* ResetData + FillEdgeData + InitCoarseFine + Integrate (depth_filler.cpp:41-56, 113-163, 233-355) on the KeyLines of `slot`, for every
+ * sequence, in-stream (no synchronisation).  Reads exactly what edgehip_download_keylines returns for the slot — for the OLD slot of
+ * a processed frame, its turned rho / s_rho (see there) — and writes nothing but the grids.  EDGEHIP_ERR_STATE if not enabled. */
+int edgehip_depth_fill(edgehip_ctx *ctx, int slot);
+/* The grid of sequence `seq` from the last edgehip_depth_fill: rho[gh*gw], s_rho[gh*gw] (depth_filler::data[].rho / .s_rho) and
+ * fixed[gh*gw] (1 where KeyLines landed: df_point::fixed), row-major.  Any of the three may be NULL.  Synchronises. */
+int edgehip_download_depth_grid(edgehip_ctx *ctx, int seq, double *rho, double *s_rho, uint8_t *fixed);
+/* The same for n sequences seqs[n] in one call (the output callbacks of a batch group): rho[j], s_rho[j], fixed[j] per request, any
+ * array or entry may be NULL.  Synchronises once. */
+int edgehip_download_depth_grids_batch(edgehip_ctx *ctx, int n, const int32_t *seqs, double *const *rho, double *const *s_rho,
+                                       uint8_t *const *fixed);
+
 /* ---- measurement ------------------------------------------------------------------------------------- */
 /* Names of the kernel groups timed by the built-in HIP-event profiler, and their accumulated device time.
  * edgehip_profile_enable(ctx, 1) brackets every launch group with events on the context stream (adds host

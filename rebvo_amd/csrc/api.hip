@@ -646,6 +646,7 @@ int edgehip_destroy(edgehip_ctx *c) {
     (void)hipStreamSynchronize(c->stream_up);
     (void)hipStreamSynchronize(c->stream_a);
     (void)hipStreamSynchronize(c->stream);
+    depth_fill_free(c);
     CtxAllocs *mine = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_allocs_mu);

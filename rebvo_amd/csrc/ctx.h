@@ -575,6 +575,9 @@ struct edgehip_ctx {
     edgehip_nav_imu *nav_imu_dev = nullptr;          // [B]
     edgehip_imu_integrated *pinned_imu = nullptr;    // [8][B] ring, like the time stamps
     edgehip_nav_imu *pinned_nav_imu = nullptr;       // [B]
+    // edgehip_depth_fill_enable: parameters, level table and device arrays of the dense depth fill (depth_fill.hip); null when off
+    struct DepthFill;
+    DepthFill *dfill = nullptr;
 };
 
 namespace edgehip {
@@ -688,5 +691,6 @@ int imu_pose_reset_enqueue(edgehip_ctx *c, int seq);   // REBVO::Reset()'s pose 
 int imu_pre_enqueue(edgehip_ctx *c, int slot_old);
 int imu_mid_enqueue(edgehip_ctx *c);
 int imu_post_enqueue(edgehip_ctx *c, int slot_new, int have_pair);
+void depth_fill_free(edgehip_ctx *c);               // depth_fill.hip: edgehip_depth_fill_enable(ctx, NULL), edgehip_destroy
 
 }  // namespace edgehip

@@ -188,6 +188,12 @@ class NavImu(C.Structure):
                 ("kn", C.c_int32), ("klm_num", C.c_int32), ("estimation_ok", C.c_int32), ("init", C.c_int32)]
 
 
+class DepthFillParams(C.Structure):
+    """edgehip_depth_fill_params: the &DepthFiller keys (PixelBlockSize, IterNum, ThreshRelRho, ThreshMatchNum) + bound mode, discard."""
+    _fields_ = [("block_w", C.c_int32), ("block_h", C.c_int32), ("iter_num", C.c_int32), ("thresh_rel_rho", C.c_double),
+                ("thresh_match_num", C.c_int32), ("bound_mode", C.c_int32), ("discard", C.c_int32)]
+
+
 NAV_DTYPE = np.dtype(Nav)   # numpy view of edgehip_nav (same offsets as the ctypes struct)
 assert NAV_DTYPE.itemsize == C.sizeof(Nav)
 
@@ -207,6 +213,8 @@ EXPORTS = [
     "edgehip_alloc_pinned", "edgehip_free_pinned", "edgehip_upload_rgb_pinned", "edgehip_upload_sync", "edgehip_upload_wait", "edgehip_register_host", "edgehip_unregister_host", "edgehip_experiments", "edgehip_fuse_stereo_depth", "edgehip_set_stereo_rig", "edgehip_get_stereo_matches", "edgehip_minimizer_v", "edgehip_ext_rot_vel",
     "edgehip_imu_enable", "edgehip_set_imu", "edgehip_read_nav_imu", "edgehip_minimizer_rv_kf", "edgehip_lm_solve",
     "edgehip_upload_grey8", "edgehip_upload_grey8_pinned", "edgehip_bind_grey8_indexed",
+    "edgehip_depth_fill_enable", "edgehip_depth_fill_size", "edgehip_depth_fill", "edgehip_download_depth_grid",
+    "edgehip_download_depth_grids_batch",
 ]
 
 _lib = None
@@ -630,6 +638,45 @@ class EdgeHip:
 
     def export_drop(self, ticket):
         self._ck(self.lib.edgehip_export_wait(self.ctx, ticket[0]))
+
+    # ---- dense depth fill (depth_filler) ----
+    def depth_fill_enable(self, block=10, iter_num=10, thresh_rel_rho=1.0, thresh_match_num=5, bound_mode=0, discard=1, block_h=None):
+        """edgehip_depth_fill_enable; block=None frees the grids.  Returns the grid size (gw, gh) or None."""
+        if block is None:
+            self._ck(self.lib.edgehip_depth_fill_enable(self.ctx, None))
+            return None
+        p = DepthFillParams(int(block), int(block if block_h is None else block_h), int(iter_num), float(thresh_rel_rho),
+                            int(thresh_match_num), int(bound_mode), int(discard))
+        self._ck(self.lib.edgehip_depth_fill_enable(self.ctx, C.byref(p)))
+        return self.depth_fill_size()
+
+    def depth_fill_size(self):
+        gw, gh = C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.edgehip_depth_fill_size(self.ctx, C.byref(gw), C.byref(gh)))
+        return gw.value, gh.value
+
+    def depth_fill(self, slot):
+        """edgehip_depth_fill: the grids of every sequence from the KeyLines of `slot` (in-stream)."""
+        self._ck(self.lib.edgehip_depth_fill(self.ctx, int(slot)))
+
+    def download_depth_grid(self, seq):
+        """-> (rho, s_rho, fixed) as (gh, gw) arrays (float64, float64, bool)."""
+        gw, gh = self.depth_fill_size()
+        rho, s_rho, fixed = np.empty((gh, gw)), np.empty((gh, gw)), np.empty((gh, gw), np.uint8)
+        self._ck(self.lib.edgehip_download_depth_grid(self.ctx, int(seq), _dp(rho), _dp(s_rho), fixed.ctypes.data_as(C.c_void_p)))
+        return rho, s_rho, fixed.astype(bool)
+
+    def download_depth_grids(self, seqs):
+        """edgehip_download_depth_grids_batch -> [(rho, s_rho, fixed)] in the order of seqs."""
+        gw, gh = self.depth_fill_size()
+        seqs = np.ascontiguousarray(seqs, dtype=np.int32)
+        n = len(seqs)
+        out = [(np.empty((gh, gw)), np.empty((gh, gw)), np.empty((gh, gw), np.uint8)) for _ in range(n)]
+        pr = (C.c_void_p * n)(*[o[0].ctypes.data for o in out])
+        ps = (C.c_void_p * n)(*[o[1].ctypes.data for o in out])
+        pf = (C.c_void_p * n)(*[o[2].ctypes.data for o in out])
+        self._ck(self.lib.edgehip_download_depth_grids_batch(self.ctx, n, seqs.ctypes.data_as(C.c_void_p), pr, ps, pf))
+        return [(r, s, f.astype(bool)) for r, s, f in out]
 
     def upload_keylines(self, seq, slot, kl, mask=None, retuned=0.0):
         kl = np.ascontiguousarray(kl, dtype=KEYLINE_DTYPE)

@@ -23,6 +23,8 @@
 // --stereo PAIRS.rgb24: every object has a stereo pair (the config's StereoAvaiable=1 and &Stereo section): pool_frames pair images, pair
 //   frame j belongs to pool frame j; each object's pair frame goes in through requestStereoCustomCamBuffer / releaseStereoCustomCamBuffer
 //   right before its main frame, with the same stamp.  The dump's last column is PipeBuffer::stereo_match_num.
+// --grid-dump PREFIX: every callback also appends to PREFIX.<i>.grid, in binary: int32 p_id, kn, gw, gh (0, 0 without a grid), the kn
+//   168-byte KeyLines of p.ef, then the PipeBuffer::depth_grid arrays rho[gh*gw] and s_rho (float64) and fixed (uint8) (&DepthFiller).
 // --snapshot-at F: object 0's TakeSnapshot() is called before its frame F is submitted (Snap0.ppm in the working directory).
 // timed over the frames after the first W of every object (default 0), from the submission of frame W to the moment every
 // object's getNav() shows its last frame.
@@ -52,10 +54,22 @@ static int tri(long k, int n) {
 }
 
 struct Sink {
-    std::ofstream dump;
+    std::ofstream dump, grid;
     std::atomic<int> calls{0};
     bool cb(PipeBuffer &p) {
         calls++;
+        if (grid.is_open()) {
+            const DepthGrid *g = p.depth_grid;
+            const int32_t hdr[4] = {p.p_id, p.ef->KNum(), g ? g->gw : 0, g ? g->gh : 0};
+            grid.write(reinterpret_cast<const char *>(hdr), sizeof hdr);
+            grid.write(reinterpret_cast<const char *>(&*p.ef->begin()), (std::streamsize)sizeof(KeyLine) * p.ef->KNum());
+            if (g) {
+                grid.write(reinterpret_cast<const char *>(g->rho.data()), (std::streamsize)(8 * g->rho.size()));
+                grid.write(reinterpret_cast<const char *>(g->s_rho.data()), (std::streamsize)(8 * g->s_rho.size()));
+                grid.write(reinterpret_cast<const char *>(g->fixed.data()), (std::streamsize)g->fixed.size());
+            }
+            grid.flush();
+        }
         if (!dump.is_open()) {
             volatile int kn = p.ef->KNum();   // a consumer that looks at the edge map
             (void)kn;
@@ -88,12 +102,12 @@ static double now_s() { return std::chrono::duration<double>(std::chrono::steady
 int main(int argn, char **argv) {
     if (argn < 8) {
         std::cout << "usage: surface_replay <GlobalConfig> <frames.rgb24> <pool_frames> <objects> <frames_per_object> <t0> <dt> "
-                     "[--group NAME] [--callback] [--dump PREFIX] [--threads T] [--warmup W]\n";
+                     "[--group NAME] [--callback] [--dump PREFIX] [--grid-dump PREFIX] [--threads T] [--warmup W]\n";
         return 2;
     }
     const int pool_frames = atoi(argv[3]), N = atoi(argv[4]), K = atoi(argv[5]);
     const double t0 = atof(argv[6]), dt = atof(argv[7]);
-    std::string group, dump_prefix, pair_file;
+    std::string group, dump_prefix, pair_file, grid_prefix;
     bool want_cb = false;
     int T = 1, W = 0, leave_obj = -1, leave_at = 0, snapshot_at = -1, dup_obj = -1, dup_at = 0, tint_obj = -1, tint_at = 0;
     bool step_mode = false, stagger = false;
@@ -102,6 +116,7 @@ int main(int argn, char **argv) {
         if (s == "--group" && a + 1 < argn) group = argv[++a];
         else if (s == "--callback") want_cb = true;
         else if (s == "--dump" && a + 1 < argn) { dump_prefix = argv[++a]; want_cb = true; }
+        else if (s == "--grid-dump" && a + 1 < argn) { grid_prefix = argv[++a]; want_cb = true; }
         else if (s == "--threads" && a + 1 < argn) T = atoi(argv[++a]);
         else if (s == "--warmup" && a + 1 < argn) W = atoi(argv[++a]);
         else if (s == "--step-mode") step_mode = true;
@@ -148,6 +163,7 @@ int main(int argn, char **argv) {
         sink.emplace_back(new Sink);
         if (!obj[i]->isInitOk()) { std::cout << "object " << i << ": bad parameters\n"; return 3; }
         if (!dump_prefix.empty()) sink[i]->dump.open(dump_prefix + "." + std::to_string(i) + ".txt");
+        if (!grid_prefix.empty()) sink[i]->grid.open(grid_prefix + "." + std::to_string(i) + ".grid", std::ios::binary);
         if (want_cb) obj[i]->setOutputCallback(&Sink::cb, sink[i].get());
     }
     phase("objects constructed");

@@ -47,6 +47,7 @@
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -268,6 +269,15 @@ struct REBVOParameters {
     // reference, rebvo_second_t.cpp:346) or Minimizer_RV<float> (what a USE_NE10 build of the reference runs, :339-343) — the run-time form of
     // the reference's compile-time switch (edgehip_set_tracker_precision).  ImuMode 0 only; members of a batch group must agree.
     int GpuTrackerPrecision = 64;
+    // &DepthFiller (app/kf_visualizer/main.cpp:56-59, src/visualizer/visualizer.cpp:559-561 of the reference): the dense inverse-depth grid of
+    // depth_filler, computed on the device from each delivered edge map and handed to the output callback as PipeBuffer::depth_grid.  Optional:
+    // absent section or PixelBlockSize = 0 = off.  BoundMode (depth_filler::bound_modes, 0..2) and Discard (FillEdgeData's discart) are ours.
+    int DF_BlockSize = 0;
+    double DF_ThreshRelRho = 1.0;
+    int DF_ThreshMatchNum = 5;
+    int DF_IterNum = 10;
+    int DF_BoundMode = 0;
+    int DF_Discard = 1;
 };
 
 // Filter state SecondThread keeps in the IMU branch (reference include/rebvo/rebvo.h:239-290, same member names).
@@ -303,6 +313,14 @@ struct NavData {
     Vector3 PoseLie = Zeros3(), Pos = Zeros3();
 };
 
+// (mirror only) The depth_filler grid of one delivered edge map: gw x gh cells of block_w x block_h pixels, row-major; rho / s_rho as
+// depth_filler::data[].rho / .s_rho, fixed = 1 where KeyLines landed (edgehip_download_depth_grid).
+struct DepthGrid {
+    int gw = 0, gh = 0, block_w = 0, block_h = 0;
+    std::vector<double> rho, s_rho;
+    std::vector<uint8_t> fixed;
+};
+
 struct PipeBuffer {
     sspace *ss = nullptr;
     global_tracker *gt = nullptr;
@@ -325,6 +343,8 @@ struct PipeBuffer {
     IntegratedImuData imu;
     bool imgc_valid = true;   // (mirror only) imgc holds THIS frame: the group engine copies the frame for the output thread only when a
                               // callback or a snapshot request is pending at launch time — per frame, not per object
+    const DepthGrid *depth_grid = nullptr;   // (mirror only) &DepthFiller on: the grid computed from exactly this buffer's ef, valid during the
+                                             // output callback; null when the fill is off or the delivery carries no KeyLines
 };
 
 namespace customCam {
@@ -364,6 +384,7 @@ class REBVO {
     std::string last_error;
     class BatchGroup;              // batch_group.cpp: the shared-context engine behind CameraType 3 / ImuMode 0 / mono objects
     friend class BatchGroup;
+    std::map<const PipeBuffer *, std::unique_ptr<DepthGrid>> df_grids;   // &DepthFiller: the grid behind each ring buffer's depth_grid
     BatchGroup *group = nullptr;
     int group_seat = -1;
     customCam::CustomCamPipeBuffer *cam_cur = nullptr;   // the buffer the application holds between request and releaseCustomCamBuffer

@@ -67,6 +67,7 @@ public:
         double t_frame = 0, t0 = 0;
         int p_num = 0;
         long frames = 0;           // frames of this member enqueued so far
+        DepthGrid df_of[4];        // [step & 3] &DepthFiller: the grid of the edge map this step's export covers (launch()), handed over by complete()
         PipeBuffer *buf_of[4] = {nullptr, nullptr, nullptr, nullptr};   // [step & 3] PipeBuffer of a step in flight (released by player 0,
                                                                         // not yet requested by player 1): later steps are enqueued first
         int ring_idx = -1;         // ring entry of the gathered frame (page-locked ring), -1: a heap image
@@ -147,6 +148,10 @@ public:
     // edgehip_process_frame): which seats it covers, and whether its copies have been enqueued yet
     struct Export { long step = -1; int ticket = 0; std::vector<int32_t> seats; bool fetched = false; };
     Export exp_of[4];              // [step & 3]
+    // &DepthFiller (the same for every member): after a step, the grids of the edge maps its callbacks get (edgehip_depth_fill on the old slot)
+    bool dfill = false;
+    edgehip_depth_fill_params dfp{};
+    int dfGrids(int slot, const std::vector<int32_t> &seq, std::vector<DepthGrid *> &dst);
     int cb_depth = 2;              // steps in flight when somebody has a callback (REBVO_GROUP_CB_DEPTH=1: the round-5 behaviour, A/B)
 
     void threadMain();
@@ -189,6 +194,13 @@ bool REBVO::groupAttach() {
         ip.acel_meas_std = params.AcelMeasStdDev; ip.g_module = params.g_module; ip.g_module_uncer = params.g_module_uncer;
         ip.g_uncert = params.g_uncert; ip.vbias_std = params.VBiasStdDev;
         ip.scale_std_mult = params.ScaleStdDevMult; ip.scale_std_max = params.ScaleStdDevMax; ip.scale_std_init = params.ScaleStdDevInit;
+    }
+    edgehip_depth_fill_params dfp;
+    std::memset(&dfp, 0, sizeof dfp);
+    const bool dfill = params.DF_BlockSize > 0;
+    if (dfill) {
+        dfp.block_w = dfp.block_h = params.DF_BlockSize; dfp.iter_num = params.DF_IterNum; dfp.thresh_rel_rho = params.DF_ThreshRelRho;
+        dfp.thresh_match_num = params.DF_ThreshMatchNum; dfp.bound_mode = params.DF_BoundMode; dfp.discard = params.DF_Discard;
     }
     auto fail = [&](const std::string &msg) {
         last_error = msg;
@@ -235,6 +247,9 @@ bool REBVO::groupAttach() {
             if (rc == 0) rc = edgehip_set_stereo_rig(g->hip, BatchGroup::kPairSlot, kTCam2Pair, kRCam2Pair, 100.0);
         }
         if (rc == 0) rc = edgehip_set_nav_log(g->hip, BatchGroup::kNavLog);
+        g->dfill = dfill;
+        g->dfp = dfp;
+        if (rc == 0 && dfill) rc = edgehip_depth_fill_enable(g->hip, &dfp);
         g->frame_bytes = (size_t)params.ImageSize.w * params.ImageSize.h * sizeof(RGB24Pixel);
         void *ringp = nullptr;
         if (rc == 0 && edgehip_alloc_pinned(g->frame_bytes * CCAMBUFSIZE * want, &ringp) == 0) g->ring = static_cast<uint8_t *>(ringp);
@@ -270,6 +285,8 @@ bool REBVO::groupAttach() {
             return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same ImuMode (0, or 1 / 2) and the same &IMU filter parameters");
         if (g->stereo != stereo || (stereo && std::memcmp(g->stereo_cam, stereo_cam, sizeof stereo_cam) != 0))
             return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same StereoAvaiable and the same &Stereo intrinsics");
+        if (g->dfill != dfill || (dfill && std::memcmp(&g->dfp, &dfp, sizeof dfp) != 0))
+            return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same &DepthFiller parameters");
     }
     std::unique_lock<std::mutex> lk(g->mut);
     if (g->started && g->attached >= g->cap) {
@@ -669,11 +686,34 @@ int REBVO::BatchGroup::launch(long step, const std::vector<double> &ts) {
             if (rc != 0) return rc;
             ex.step = step;
             ex.fetched = false;
+            if (dfill) {   // the grids of the same edge maps (the old slot), read back now: the next step's fill reuses the device grids
+                std::vector<DepthGrid *> dst;
+                for (int seat : ex.seats) dst.push_back(&seats[seat].df_of[step & 3]);
+                rc = dfGrids((edgehip_cur_slot(hip) + 2) % 3, ex.seats, dst);
+                if (rc != 0) return rc;
+            }
         }
     }
     tm.buffers += detail::now_s() - tp1;
     tm.steps++;
     return 0;
+}
+
+// edgehip_depth_fill on `slot` for all sequences, then the grids of sequences seq[j] into dst[j] (synchronises)
+int REBVO::BatchGroup::dfGrids(int slot, const std::vector<int32_t> &seq, std::vector<DepthGrid *> &dst) {
+    int rc = edgehip_depth_fill(hip, slot);
+    int32_t gw = 0, gh = 0;
+    if (rc == 0) rc = edgehip_depth_fill_size(hip, &gw, &gh);
+    if (rc != 0) return rc;
+    std::vector<double *> r(seq.size()), s(seq.size());
+    std::vector<uint8_t *> f(seq.size());
+    for (size_t j = 0; j < seq.size(); j++) {
+        DepthGrid &g = *dst[j];
+        g.gw = gw; g.gh = gh; g.block_w = dfp.block_w; g.block_h = dfp.block_h;
+        g.rho.resize((size_t)gw * gh); g.s_rho.resize((size_t)gw * gh); g.fixed.resize((size_t)gw * gh);
+        r[j] = g.rho.data(); s[j] = g.s_rho.data(); f[j] = g.fixed.data();
+    }
+    return edgehip_download_depth_grids_batch(hip, (int)seq.size(), seq.data(), r.data(), s.data(), f.data());
 }
 
 int REBVO::BatchGroup::exportFetch(Export &ex, const std::vector<int32_t> &kn, const std::vector<edgehip_keyline *> &dst) {
@@ -755,6 +795,13 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
         if (st.have_prev) {   // the frame before goes to the output thread, with its edge map as this frame's tracking left it
             PipeBuffer &ob = cf->pipe.RequestBuffer(1);
             deliver[i] = &ob;
+            ob.depth_grid = nullptr;
+            if (dfill && cf->haveCallBack() && cb_depth > 1 && in_export(i)) {   // the grid of exactly the lists exported with this step
+                std::unique_ptr<DepthGrid> &gd = cf->df_grids[&ob];
+                if (!gd) gd.reset(new DepthGrid);
+                std::swap(*gd, st.df_of[step & 3]);
+                ob.depth_grid = gd.get();
+            }
             if (cf->haveCallBack() && cb_depth > 1) {
                 // the lists were packed behind this step (launch()); a callback registered after that gets this one delivery without
                 // KeyLines — the ring slot may have been detected into again — and the next with them
@@ -777,6 +824,16 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
         rc = edgehip_download_keylines_batch(hip, slot_before, (int)cb_seq.size(), cb_seq.data(), cb_dst.data(), kn.data());
         if (rc != 0) std::cout << "\nREBVO: edgehip_download_keylines_batch failed: " << edgehip_last_error() << "\n";
         for (size_t j = 0; j < cb_buf.size(); j++) cb_buf[j]->ef->kn = rc == 0 ? kn[j] : 0;
+        if (rc == 0 && dfill) {   // the grids of the same lists
+            std::vector<DepthGrid *> dst;
+            for (size_t j = 0; j < cb_buf.size(); j++) {
+                std::unique_ptr<DepthGrid> &gd = seats[cb_seq[j]].cf->df_grids[cb_buf[j]];
+                if (!gd) gd.reset(new DepthGrid);
+                dst.push_back(gd.get());
+            }
+            rc = dfGrids(slot_before, cb_seq, dst);
+            for (size_t j = 0; j < cb_buf.size(); j++) cb_buf[j]->depth_grid = rc == 0 ? dst[j] : nullptr;
+        }
     }
     if (have_ex) {
         // this step's export: the lists of the frames about to be delivered.  Normally its copies were enqueued one completion ago
@@ -982,6 +1039,37 @@ extern "C" int rebvo_group_selftest(const char *config_file) {
     p.GpuBatchSize = 0;
     REBVO z(p);
     if (z.Init()) return 11;                                   // a named group needs BatchSize >= 1
+    return 0;
+}
+
+// Members of one group with other &DepthFiller parameters are refused at Init() (GPU test hook, like rebvo_group_selftest): 0 = as expected
+extern "C" int rebvo_group_depth_fill_selftest(const char *config_file) {
+    using namespace rebvo;
+    REBVO proto(config_file);
+    if (!proto.isInitOk()) return 1;
+    REBVOParameters p = proto.getParams();
+    p.CameraType = 3; p.ImuMode = 0; p.StereoAvaiable = false;
+    p.GpuBatchGroup = "df_selftest";
+    p.GpuBatchSize = 2;
+    p.DF_BlockSize = 10;
+    REBVO a(p);
+    if (!a.Init()) return 2;
+    REBVOParameters q = p;
+    q.DF_BlockSize = 5;
+    REBVO b(q);
+    if (b.Init() || b.lastError().find("DepthFiller") == std::string::npos) return 3;   // another block size
+    q = p;
+    q.DF_BlockSize = 0;
+    REBVO c(q);
+    if (c.Init() || c.lastError().find("DepthFiller") == std::string::npos) return 4;   // fill off beside fill on
+    q = p;
+    q.DF_Discard = 0;
+    REBVO d(q);
+    if (d.Init() || d.lastError().find("DepthFiller") == std::string::npos) return 5;
+    REBVO e(p);
+    if (!e.Init()) return 6;                                                              // the same parameters: the group starts
+    a.CleanUp();
+    e.CleanUp();
     return 0;
 }
 

@@ -305,6 +305,12 @@ REBVO::REBVO(const char *configFile)
         int tprec = 64;
         if (config.get("GPU", "TrackerPrecision", tprec, false)) p.GpuTrackerPrecision = tprec;
     }
+    config.get("DepthFiller", "PixelBlockSize", p.DF_BlockSize, false);   // optional section: no key of it is mandatory
+    config.get("DepthFiller", "ThreshRelRho", p.DF_ThreshRelRho, false);
+    config.get("DepthFiller", "ThreshMatchNum", p.DF_ThreshMatchNum, false);
+    config.get("DepthFiller", "IterNum", p.DF_IterNum, false);
+    config.get("DepthFiller", "BoundMode", p.DF_BoundMode, false);
+    config.get("DepthFiller", "Discard", p.DF_Discard, false);
     construct();
 }
 
