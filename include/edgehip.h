@@ -496,6 +496,55 @@ int edgehip_download_depth_grid(edgehip_ctx *ctx, int seq, double *rho, double *
 int edgehip_download_depth_grids_batch(edgehip_ctx *ctx, int n, const int32_t *seqs, double *const *rho, double *const *s_rho,
                                        uint8_t *const *fixed);
 
+/* ---- depth surface (what depth_filler's callers take from the grid) --------------------------------------------------------
+ * From the grids of the last edgehip_depth_fill, for every sequence, in the camera frame and bit for bit as depth_filler computes them
+ * (tests/depth_surface_port.py restates it), except the sign and payload of a NaN the arithmetic creates:
+ *   per cell (surface != 0), cell (x, y) at y * gw + x:
+ *     point[3]  get3DPos(x, y) (include/visualizer/depth_filler.h:115-122, gl_viewer.cpp / surface_integrator.cpp:48, 93)
+ *     dist      computeDistance(Zeros) (depth_filler.cpp:170-180, visualizer.cpp:436-440, keyframe.cpp:181): |point|
+ *     min_dist  one per sequence: current_min_dist / GetMinDist() of the same call (1e20 when every dist is NaN)
+ *     normal[3] calcSurfNormals (depth_filler.cpp:358-373): the value its raster loop leaves — a cell's own computation for x <= gw-2,
+ *               y <= gh-2, else that of (x-1, y-1)
+ *     area      calcSurfArea (depth_filler.cpp:377-389), float as df_point::area
+ *   One departure, where the reference has no defined result: the cells calcSurfNormals never writes ((gw-1, 0), (0, gh-1), every
+ *   cell of a grid 1 cell wide or high) and calcSurfArea never writes (the last row and column) hold NaN; the reference leaves them
+ *   uninitialised.
+ *   per pixel (image_mode), at every integer pixel (px, py) of the w x h image, rho[py][px] and s_rho[py][px] as float (both
+ *   functions compute in float: exact): getImgRho(px, py, &s_rho) (depth_filler.h:246-280, gl_viewer.cpp:562-602) or
+ *   getImgRhoTriInterp(px, py, &s_rho) (depth_filler.h:203-244, its s_rho formula as written). */
+typedef enum edgehip_depth_image_mode {
+    EDGEHIP_DEPTH_IMAGE_OFF = 0,
+    EDGEHIP_DEPTH_IMAGE_BILINEAR = 1,   /* getImgRho */
+    EDGEHIP_DEPTH_IMAGE_TRIANGLE = 2    /* getImgRhoTriInterp */
+} edgehip_depth_image_mode;
+typedef struct edgehip_depth_surface_params {
+    int32_t surface;      /* != 0: per-cell point / normal / area / dist / min_dist */
+    int32_t image_mode;   /* edgehip_depth_image_mode */
+} edgehip_depth_surface_params;
+/* Allocates the products for every sequence: 60 B per cell (+ 8 B per sequence) for the surface, w * h * 8 B for the image.
+ * params == NULL, or both products off, frees them.  EDGEHIP_ERR_STATE while the fill is off, EDGEHIP_ERR_ARG for an unknown
+ * image_mode, EDGEHIP_ERR_MEMORY when the allocation fails (the products are then off; the context stays usable).  Disabling the
+ * fill, or enabling it with other block sizes, frees them too. */
+int edgehip_depth_surface_enable(edgehip_ctx *ctx, const edgehip_depth_surface_params *params);
+/* computeDistance(Zeros) + calcSurfNormals + calcSurfArea and / or the image, from the grids of the last edgehip_depth_fill, for
+ * every sequence, in-stream (no synchronisation).  EDGEHIP_ERR_STATE when not enabled or before the first fill since the fill's
+ * enable. */
+int edgehip_depth_surface(edgehip_ctx *ctx);
+/* The per-cell products of sequence `seq`: point[3 gh gw], normal[3 gh gw], area[gh gw], dist[gh gw], min_dist[1].  Any may be NULL.
+ * Synchronises.  EDGEHIP_ERR_STATE when the surface is not enabled. */
+int edgehip_download_depth_surface(edgehip_ctx *ctx, int seq, double *point, double *normal, float *area, double *dist, double *min_dist);
+/* The same for n sequences seqs[n] (point[j], ... per request; any array or entry may be NULL).  Synchronises once. */
+int edgehip_download_depth_surfaces_batch(edgehip_ctx *ctx, int n, const int32_t *seqs, double *const *point, double *const *normal,
+                                          float *const *area, double *const *dist, double *const *min_dist);
+/* The depth image of sequence `seq`: rho[h w], s_rho[h w] (row-major; either may be NULL).  Synchronises.  EDGEHIP_ERR_STATE when
+ * the image is not enabled. */
+int edgehip_download_depth_image(edgehip_ctx *ctx, int seq, float *rho, float *s_rho);
+/* The same for n sequences seqs[n] in one call.  Synchronises once. */
+int edgehip_download_depth_images_batch(edgehip_ctx *ctx, int n, const int32_t *seqs, float *const *rho, float *const *s_rho);
+/* The images of sequences [first, first+count) into DEVICE memory of the context's GPU, rho_dev[count][h][w] and s_rho_dev[count][h][w]
+ * (either may be NULL; e.g. torch tensors), without a host bounce — like edgehip_read_nav_log_device.  The copy is complete on return. */
+int edgehip_depth_image_device(edgehip_ctx *ctx, int first, int count, float *rho_dev, float *s_rho_dev);
+
 /* ---- measurement ------------------------------------------------------------------------------------- */
 /* Names of the kernel groups timed by the built-in HIP-event profiler, and their accumulated device time.
  * edgehip_profile_enable(ctx, 1) brackets every launch group with events on the context stream (adds host

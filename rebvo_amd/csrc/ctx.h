@@ -578,6 +578,9 @@ struct edgehip_ctx {
     // edgehip_depth_fill_enable: parameters, level table and device arrays of the dense depth fill (depth_fill.hip); null when off
     struct DepthFill;
     DepthFill *dfill = nullptr;
+    // edgehip_depth_surface_enable: per-cell surface and per-pixel depth image from the fill's grids (depth_surface.hip); null when off
+    struct DepthSurface;
+    DepthSurface *dsurf = nullptr;
 };
 
 namespace edgehip {
@@ -691,6 +694,9 @@ int imu_pose_reset_enqueue(edgehip_ctx *c, int seq);   // REBVO::Reset()'s pose 
 int imu_pre_enqueue(edgehip_ctx *c, int slot_old);
 int imu_mid_enqueue(edgehip_ctx *c);
 int imu_post_enqueue(edgehip_ctx *c, int slot_new, int have_pair);
-void depth_fill_free(edgehip_ctx *c);               // depth_fill.hip: edgehip_depth_fill_enable(ctx, NULL), edgehip_destroy
+void depth_fill_free(edgehip_ctx *c);               // depth_fill.hip: edgehip_depth_fill_enable(ctx, NULL), edgehip_destroy (frees the surface too)
+int depth_fill_geometry(edgehip_ctx *c, int32_t *gw, int32_t *gh, int32_t *bw, int32_t *bh);   // depth_fill.hip: EDGEHIP_ERR_STATE when off
+bool depth_fill_grids(edgehip_ctx *c, const double **rho, const double **s_rho);   // depth_fill.hip: false before the first fill
+void depth_surface_free(edgehip_ctx *c);            // depth_surface.hip
 
 }  // namespace edgehip

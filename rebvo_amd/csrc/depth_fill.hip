@@ -269,14 +269,33 @@ struct edgehip_ctx::DepthFill {
     int32_t *cell, *cnt, *off, *ids, *tile_n;
     double *tile_r, *tile_s, *rho, *s_rho;
     uint8_t *fixed;
+    bool filled = false;   // an edgehip_depth_fill was enqueued since the enable
 };
 
-void edgehip::depth_fill_free(edgehip_ctx *c) {
+static void depth_fill_release(edgehip_ctx *c) {
     if (!c->dfill) return;
     (void)hipStreamSynchronize(c->stream);
     if (c->dfill->arena) (void)hipFree(c->dfill->arena);
     delete c->dfill;
     c->dfill = nullptr;
+}
+
+void edgehip::depth_fill_free(edgehip_ctx *c) {
+    depth_surface_free(c);
+    depth_fill_release(c);
+}
+
+int edgehip::depth_fill_geometry(edgehip_ctx *c, int32_t *gw, int32_t *gh, int32_t *bw, int32_t *bh) {
+    if (!c->dfill) return EDGEHIP_ERR_STATE;
+    *gw = c->dfill->gw; *gh = c->dfill->gh; *bw = c->dfill->p.block_w; *bh = c->dfill->p.block_h;
+    return 0;
+}
+
+bool edgehip::depth_fill_grids(edgehip_ctx *c, const double **rho, const double **s_rho) {
+    if (!c->dfill || !c->dfill->filled) return false;
+    *rho = c->dfill->rho;
+    *s_rho = c->dfill->s_rho;
+    return true;
 }
 
 int edgehip_depth_fill_enable(edgehip_ctx *c, const edgehip_depth_fill_params *p) {
@@ -288,7 +307,9 @@ int edgehip_depth_fill_enable(edgehip_ctx *c, const edgehip_depth_fill_params *p
     }
     const int gw = c->plan.w / p->block_w, gh = c->plan.h / p->block_h;
     if (gw < 1 || gh < 1) { set_error("depth_fill_enable: the grid (image size / block size) is smaller than 1x1"); return EDGEHIP_ERR_ARG; }
-    depth_fill_free(c);
+    // the depth surface stays enabled while the blocks (and so the grid) stay the same; it reads the new grids after the next fill
+    if (c->dfill && (c->dfill->p.block_w != p->block_w || c->dfill->p.block_h != p->block_h)) depth_surface_free(c);
+    depth_fill_release(c);
     auto *d = new edgehip_ctx::DepthFill;
     d->p = *p;
     d->gw = gw;
@@ -311,6 +332,7 @@ int edgehip_depth_fill_enable(edgehip_ctx *c, const edgehip_depth_fill_params *p
     if (hipMalloc(&d->arena, bytes) != hipSuccess) {
         (void)hipGetLastError();
         delete d;
+        depth_surface_free(c);
         set_error("depth_fill_enable: device allocation failed");
         return EDGEHIP_ERR_MEMORY;
     }
@@ -330,6 +352,7 @@ int edgehip_depth_fill_enable(edgehip_ctx *c, const edgehip_depth_fill_params *p
         (void)hipGetLastError();
         (void)hipFree(d->arena);
         delete d;
+        depth_surface_free(c);
         set_error("depth_fill_enable: hipMemsetAsync failed");
         return EDGEHIP_ERR_DEVICE;
     }
@@ -367,6 +390,7 @@ int edgehip_depth_fill(edgehip_ctx *c, int slot) {
     const size_t lds = d->use_lds ? (size_t)d->gw * d->gh * 17 : 0;
     hipLaunchKernelGGL(k_depth_fill, dim3(c->plan.nseq), dim3(kDfThreads), lds, c->stream, a, d->lv);
     EH_LAUNCH_CHECK();
+    d->filled = true;
     if (c->stream_a != c->stream) {   // a later stage A that detects into this slot waits for the fill's reads
         EH_CHECK(hipEventRecord(c->ev_use[slot], c->stream));
         c->use_valid[slot] = true;

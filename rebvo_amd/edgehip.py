@@ -194,6 +194,11 @@ class DepthFillParams(C.Structure):
                 ("thresh_match_num", C.c_int32), ("bound_mode", C.c_int32), ("discard", C.c_int32)]
 
 
+class DepthSurfaceParams(C.Structure):
+    """edgehip_depth_surface_params: per-cell surface on / off, depth image mode (0 off, 1 getImgRho, 2 getImgRhoTriInterp)."""
+    _fields_ = [("surface", C.c_int32), ("image_mode", C.c_int32)]
+
+
 NAV_DTYPE = np.dtype(Nav)   # numpy view of edgehip_nav (same offsets as the ctypes struct)
 assert NAV_DTYPE.itemsize == C.sizeof(Nav)
 
@@ -215,6 +220,8 @@ EXPORTS = [
     "edgehip_upload_grey8", "edgehip_upload_grey8_pinned", "edgehip_bind_grey8_indexed",
     "edgehip_depth_fill_enable", "edgehip_depth_fill_size", "edgehip_depth_fill", "edgehip_download_depth_grid",
     "edgehip_download_depth_grids_batch",
+    "edgehip_depth_surface_enable", "edgehip_depth_surface", "edgehip_download_depth_surface", "edgehip_download_depth_surfaces_batch",
+    "edgehip_download_depth_image", "edgehip_download_depth_images_batch", "edgehip_depth_image_device",
 ]
 
 _lib = None
@@ -677,6 +684,72 @@ class EdgeHip:
         pf = (C.c_void_p * n)(*[o[2].ctypes.data for o in out])
         self._ck(self.lib.edgehip_download_depth_grids_batch(self.ctx, n, seqs.ctypes.data_as(C.c_void_p), pr, ps, pf))
         return [(r, s, f.astype(bool)) for r, s, f in out]
+
+    # ---- depth surface (computeDistance / calcSurfNormals / calcSurfArea / getImgRho*) ----
+    def depth_surface_enable(self, surface=True, image_mode=0):
+        """edgehip_depth_surface_enable; surface=None frees the products.  image_mode: 0 off, 1 getImgRho, 2 getImgRhoTriInterp."""
+        if surface is None:
+            self._ck(self.lib.edgehip_depth_surface_enable(self.ctx, None))
+            return
+        p = DepthSurfaceParams(int(bool(surface)), int(image_mode))
+        self._ck(self.lib.edgehip_depth_surface_enable(self.ctx, C.byref(p)))
+
+    def depth_surface(self):
+        """edgehip_depth_surface: the enabled products of every sequence from the last fill's grids (in-stream)."""
+        self._ck(self.lib.edgehip_depth_surface(self.ctx))
+
+    def download_depth_surfaces(self, seqs):
+        """edgehip_download_depth_surfaces_batch -> [dict(point (gh, gw, 3), normal (gh, gw, 3), area (gh, gw) float32,
+        dist (gh, gw), min_dist float)] in the order of seqs."""
+        gw, gh = self.depth_fill_size()
+        seqs = np.ascontiguousarray(seqs, dtype=np.int32)
+        n = len(seqs)
+        out = [dict(point=np.empty((gh, gw, 3)), normal=np.empty((gh, gw, 3)), area=np.empty((gh, gw), np.float32),
+                    dist=np.empty((gh, gw)), min_dist=np.empty(1)) for _ in range(n)]
+        ptrs = [(C.c_void_p * n)(*[o[k].ctypes.data for o in out]) for k in ("point", "normal", "area", "dist", "min_dist")]
+        self._ck(self.lib.edgehip_download_depth_surfaces_batch(self.ctx, n, seqs.ctypes.data_as(C.c_void_p), *ptrs))
+        for o in out:
+            o["min_dist"] = float(o["min_dist"][0])
+        return out
+
+    def download_depth_surface(self, seq):
+        """edgehip_download_depth_surface -> dict(point, normal, area, dist, min_dist) as download_depth_surfaces."""
+        gw, gh = self.depth_fill_size()
+        o = dict(point=np.empty((gh, gw, 3)), normal=np.empty((gh, gw, 3)), area=np.empty((gh, gw), np.float32),
+                 dist=np.empty((gh, gw)), min_dist=np.empty(1))
+        self._ck(self.lib.edgehip_download_depth_surface(self.ctx, int(seq), *[C.c_void_p(o[k].ctypes.data) for k in
+                                                                               ("point", "normal", "area", "dist", "min_dist")]))
+        o["min_dist"] = float(o["min_dist"][0])
+        return o
+
+    def download_depth_images(self, seqs):
+        """edgehip_download_depth_images_batch -> [(rho, s_rho)] as (h, w) float32 arrays, in the order of seqs."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.int32)
+        n = len(seqs)
+        out = [(np.empty((self.h, self.w), np.float32), np.empty((self.h, self.w), np.float32)) for _ in range(n)]
+        pr = (C.c_void_p * n)(*[o[0].ctypes.data for o in out])
+        ps = (C.c_void_p * n)(*[o[1].ctypes.data for o in out])
+        self._ck(self.lib.edgehip_download_depth_images_batch(self.ctx, n, seqs.ctypes.data_as(C.c_void_p), pr, ps))
+        return out
+
+    def download_depth_image(self, seq):
+        """edgehip_download_depth_image -> (rho, s_rho) as (h, w) float32 arrays."""
+        rho, s_rho = np.empty((self.h, self.w), np.float32), np.empty((self.h, self.w), np.float32)
+        self._ck(self.lib.edgehip_download_depth_image(self.ctx, int(seq), C.c_void_p(rho.ctypes.data), C.c_void_p(s_rho.ctypes.data)))
+        return rho, s_rho
+
+    def depth_image_into(self, rho, s_rho=None, first=0):
+        """edgehip_depth_image_device: the images of sequences [first, first + len(rho)) into float32 torch tensors of shape
+        (count, h, w) on the context's device (either may be None), device to device."""
+        t = rho if rho is not None else s_rho
+        count = t.shape[0]
+        for x in (rho, s_rho):
+            if x is not None:
+                assert x.dtype.itemsize == 4 and x.is_floating_point() and x.is_contiguous(), "float32 contiguous tensors"
+                assert tuple(x.shape) == (count, self.h, self.w), (tuple(x.shape), (count, self.h, self.w))
+        self._ck(self.lib.edgehip_depth_image_device(self.ctx, int(first), int(count),
+                                                     C.c_void_p(rho.data_ptr() if rho is not None else None),
+                                                     C.c_void_p(s_rho.data_ptr() if s_rho is not None else None)))
 
     def upload_keylines(self, seq, slot, kl, mask=None, retuned=0.0):
         kl = np.ascontiguousarray(kl, dtype=KEYLINE_DTYPE)

@@ -25,6 +25,14 @@
 //   right before its main frame, with the same stamp.  The dump's last column is PipeBuffer::stereo_match_num.
 // --grid-dump PREFIX: every callback also appends to PREFIX.<i>.grid, in binary: int32 p_id, kn, gw, gh (0, 0 without a grid), the kn
 //   168-byte KeyLines of p.ef, then the PipeBuffer::depth_grid arrays rho[gh*gw] and s_rho (float64) and fixed (uint8) (&DepthFiller).
+// --surface-dump PREFIX: every callback also appends to PREFIX.<i>.surf, in binary: int32 p_id, gw, gh, has_surface, w, h, mode (0 where
+//   a product is absent), float64 nav.Pose[3][3], nav.Pos[3] and K, the PipeBuffer::depth_grid arrays rho and s_rho (float64), then
+//   PipeBuffer::depth_surface's point[3 gh gw], normal[3 gh gw],
+//   dist[gh gw], min_dist (float64) and area[gh gw] (float32), then PipeBuffer::depth_image's rho[h w] and s_rho[h w] (float32)
+//   (&DepthFiller Surface / DenseImage).
+// --ply DIR [--ply-every N]: for every N-th callback of each object (default 1) with a depth_surface, DIR/obj<i>_<p_id>.ply: a binary
+//   little-endian PLY of the cells with a finite point, their normals, in the world frame — Local2WorldScaled
+//   (include/mtracklib/keyframe.h:101-103 of the reference: Pose * p * K + Pos) from the buffer's nav.Pose, nav.Pos and K.
 // --snapshot-at F: object 0's TakeSnapshot() is called before its frame F is submitted (Snap0.ppm in the working directory).
 // timed over the frames after the first W of every object (default 0), from the submission of frame W to the moment every
 // object's getNav() shows its last frame.
@@ -54,10 +62,66 @@ static int tri(long k, int n) {
 }
 
 struct Sink {
-    std::ofstream dump, grid;
+    std::ofstream dump, grid, surf;
+    std::string ply_dir;
+    int ply_every = 1, obj = 0;
     std::atomic<int> calls{0};
+    void writeSurface(const PipeBuffer &p) {
+        const DepthGrid *g = p.depth_grid;
+        const DepthSurface *d = p.depth_surface;
+        const DepthImage *m = p.depth_image;
+        const int32_t hdr[7] = {p.p_id, g ? g->gw : 0, g ? g->gh : 0, d ? 1 : 0, m ? m->w : 0, m ? m->h : 0, m ? m->mode : 0};
+        surf.write(reinterpret_cast<const char *>(hdr), sizeof hdr);
+        double pose[13];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) pose[3 * i + j] = p.nav.Pose(i, j);
+        for (int i = 0; i < 3; i++) pose[9 + i] = p.nav.Pos[i];
+        pose[12] = p.K;
+        surf.write(reinterpret_cast<const char *>(pose), sizeof pose);
+        if (g) {
+            surf.write(reinterpret_cast<const char *>(g->rho.data()), (std::streamsize)(8 * g->rho.size()));
+            surf.write(reinterpret_cast<const char *>(g->s_rho.data()), (std::streamsize)(8 * g->s_rho.size()));
+        }
+        if (d) {
+            surf.write(reinterpret_cast<const char *>(d->point.data()), (std::streamsize)(8 * d->point.size()));
+            surf.write(reinterpret_cast<const char *>(d->normal.data()), (std::streamsize)(8 * d->normal.size()));
+            surf.write(reinterpret_cast<const char *>(d->dist.data()), (std::streamsize)(8 * d->dist.size()));
+            surf.write(reinterpret_cast<const char *>(&d->min_dist), 8);
+            surf.write(reinterpret_cast<const char *>(d->area.data()), (std::streamsize)(4 * d->area.size()));
+        }
+        if (m) {
+            surf.write(reinterpret_cast<const char *>(m->rho.data()), (std::streamsize)(4 * m->rho.size()));
+            surf.write(reinterpret_cast<const char *>(m->s_rho.data()), (std::streamsize)(4 * m->s_rho.size()));
+        }
+        surf.flush();
+    }
+    void writePly(const PipeBuffer &p) {   // the finite cell points with their normals, camera frame -> world frame on the host
+        const DepthSurface *d = p.depth_surface;
+        std::vector<float> v;
+        const size_t G = (size_t)d->gw * d->gh;
+        for (size_t c = 0; c < G; c++) {
+            const double *P = &d->point[3 * c], *N = &d->normal[3 * c];
+            if (!std::isfinite(P[0]) || !std::isfinite(P[1]) || !std::isfinite(P[2])) continue;
+            for (int i = 0; i < 3; i++) {   // Local2WorldScaled: Pose * P * K + Pos
+                double s = 0;
+                for (int j = 0; j < 3; j++) s += p.nav.Pose(i, j) * P[j];
+                v.push_back((float)(s * p.K + p.nav.Pos[i]));
+            }
+            for (int i = 0; i < 3; i++) {   // normals turn with the pose
+                double s = 0;
+                for (int j = 0; j < 3; j++) s += p.nav.Pose(i, j) * N[j];
+                v.push_back((float)s);
+            }
+        }
+        std::ofstream f(ply_dir + "/obj" + std::to_string(obj) + "_" + std::to_string(p.p_id) + ".ply", std::ios::binary);
+        f << "ply\nformat binary_little_endian 1.0\nelement vertex " << v.size() / 6
+          << "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\nend_header\n";
+        f.write(reinterpret_cast<const char *>(v.data()), (std::streamsize)(4 * v.size()));
+    }
     bool cb(PipeBuffer &p) {
-        calls++;
+        const int call = calls++;
+        if (surf.is_open()) writeSurface(p);
+        if (!ply_dir.empty() && p.depth_surface && call % ply_every == 0) writePly(p);
         if (grid.is_open()) {
             const DepthGrid *g = p.depth_grid;
             const int32_t hdr[4] = {p.p_id, p.ef->KNum(), g ? g->gw : 0, g ? g->gh : 0};
@@ -102,12 +166,13 @@ static double now_s() { return std::chrono::duration<double>(std::chrono::steady
 int main(int argn, char **argv) {
     if (argn < 8) {
         std::cout << "usage: surface_replay <GlobalConfig> <frames.rgb24> <pool_frames> <objects> <frames_per_object> <t0> <dt> "
-                     "[--group NAME] [--callback] [--dump PREFIX] [--grid-dump PREFIX] [--threads T] [--warmup W]\n";
+                     "[--group NAME] [--callback] [--dump PREFIX] [--grid-dump PREFIX] [--surface-dump PREFIX] [--ply DIR [--ply-every N]] [--threads T] [--warmup W]\n";
         return 2;
     }
     const int pool_frames = atoi(argv[3]), N = atoi(argv[4]), K = atoi(argv[5]);
     const double t0 = atof(argv[6]), dt = atof(argv[7]);
-    std::string group, dump_prefix, pair_file, grid_prefix;
+    std::string group, dump_prefix, pair_file, grid_prefix, surf_prefix, ply_dir;
+    int ply_every = 1;
     bool want_cb = false;
     int T = 1, W = 0, leave_obj = -1, leave_at = 0, snapshot_at = -1, dup_obj = -1, dup_at = 0, tint_obj = -1, tint_at = 0;
     bool step_mode = false, stagger = false;
@@ -117,6 +182,9 @@ int main(int argn, char **argv) {
         else if (s == "--callback") want_cb = true;
         else if (s == "--dump" && a + 1 < argn) { dump_prefix = argv[++a]; want_cb = true; }
         else if (s == "--grid-dump" && a + 1 < argn) { grid_prefix = argv[++a]; want_cb = true; }
+        else if (s == "--surface-dump" && a + 1 < argn) { surf_prefix = argv[++a]; want_cb = true; }
+        else if (s == "--ply" && a + 1 < argn) { ply_dir = argv[++a]; want_cb = true; }
+        else if (s == "--ply-every" && a + 1 < argn) ply_every = std::max(1, atoi(argv[++a]));
         else if (s == "--threads" && a + 1 < argn) T = atoi(argv[++a]);
         else if (s == "--warmup" && a + 1 < argn) W = atoi(argv[++a]);
         else if (s == "--step-mode") step_mode = true;
@@ -164,6 +232,10 @@ int main(int argn, char **argv) {
         if (!obj[i]->isInitOk()) { std::cout << "object " << i << ": bad parameters\n"; return 3; }
         if (!dump_prefix.empty()) sink[i]->dump.open(dump_prefix + "." + std::to_string(i) + ".txt");
         if (!grid_prefix.empty()) sink[i]->grid.open(grid_prefix + "." + std::to_string(i) + ".grid", std::ios::binary);
+        if (!surf_prefix.empty()) sink[i]->surf.open(surf_prefix + "." + std::to_string(i) + ".surf", std::ios::binary);
+        sink[i]->ply_dir = ply_dir;
+        sink[i]->ply_every = ply_every;
+        sink[i]->obj = i;
         if (want_cb) obj[i]->setOutputCallback(&Sink::cb, sink[i].get());
     }
     phase("objects constructed");

@@ -278,6 +278,11 @@ struct REBVOParameters {
     int DF_IterNum = 10;
     int DF_BoundMode = 0;
     int DF_Discard = 1;
+    // &DepthFiller Surface (0 / 1) and DenseImage (0 off, 1 getImgRho, 2 getImgRhoTriInterp), ours: what the reference's callers take from the
+    // grid (computeDistance, get3DPos, calcSurfNormals, calcSurfArea; the per-pixel depth image), computed on the device after the fill and
+    // handed over as PipeBuffer::depth_surface / depth_image.  Ignored while the fill is off.
+    int DF_Surface = 0;
+    int DF_DenseImage = 0;
 };
 
 // Filter state SecondThread keeps in the IMU branch (reference include/rebvo/rebvo.h:239-290, same member names).
@@ -321,6 +326,23 @@ struct DepthGrid {
     std::vector<uint8_t> fixed;
 };
 
+// (mirror only) What depth_filler's callers take from that grid (edgehip_download_depth_surface), in the camera frame: per cell (x, y) at
+// y * gw + x, point[3] = get3DPos, normal[3] (calcSurfNormals), area (calcSurfArea), dist (computeDistance(Zeros)); min_dist = GetMinDist().
+// NaN where the reference never writes a normal or an area (include/edgehip.h).
+struct DepthSurface {
+    int gw = 0, gh = 0;
+    std::vector<double> point, normal, dist;
+    std::vector<float> area;
+    double min_dist = 0;
+};
+
+// (mirror only) The per-pixel depth image of that grid (edgehip_download_depth_image): rho / s_rho [h][w] of getImgRho (mode 1) or
+// getImgRhoTriInterp (mode 2) at every integer pixel.
+struct DepthImage {
+    int w = 0, h = 0, mode = 0;
+    std::vector<float> rho, s_rho;
+};
+
 struct PipeBuffer {
     sspace *ss = nullptr;
     global_tracker *gt = nullptr;
@@ -345,6 +367,8 @@ struct PipeBuffer {
                               // callback or a snapshot request is pending at launch time — per frame, not per object
     const DepthGrid *depth_grid = nullptr;   // (mirror only) &DepthFiller on: the grid computed from exactly this buffer's ef, valid during the
                                              // output callback; null when the fill is off or the delivery carries no KeyLines
+    const DepthSurface *depth_surface = nullptr;   // (mirror only) &DepthFiller Surface = 1: from exactly depth_grid, same lifetime; else null
+    const DepthImage *depth_image = nullptr;       // (mirror only) &DepthFiller DenseImage = 1 / 2: likewise
 };
 
 namespace customCam {
@@ -385,6 +409,8 @@ class REBVO {
     class BatchGroup;              // batch_group.cpp: the shared-context engine behind CameraType 3 / ImuMode 0 / mono objects
     friend class BatchGroup;
     std::map<const PipeBuffer *, std::unique_ptr<DepthGrid>> df_grids;   // &DepthFiller: the grid behind each ring buffer's depth_grid
+    std::map<const PipeBuffer *, std::unique_ptr<DepthSurface>> df_surfs;   // ... and its surface / image (Surface, DenseImage)
+    std::map<const PipeBuffer *, std::unique_ptr<DepthImage>> df_images;
     BatchGroup *group = nullptr;
     int group_seat = -1;
     customCam::CustomCamPipeBuffer *cam_cur = nullptr;   // the buffer the application holds between request and releaseCustomCamBuffer

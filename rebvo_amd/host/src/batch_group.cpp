@@ -68,6 +68,8 @@ public:
         int p_num = 0;
         long frames = 0;           // frames of this member enqueued so far
         DepthGrid df_of[4];        // [step & 3] &DepthFiller: the grid of the edge map this step's export covers (launch()), handed over by complete()
+        DepthSurface ds_of[4];     // [step & 3] ... its surface and image (Surface, DenseImage), handed over with it
+        DepthImage di_of[4];
         PipeBuffer *buf_of[4] = {nullptr, nullptr, nullptr, nullptr};   // [step & 3] PipeBuffer of a step in flight (released by player 0,
                                                                         // not yet requested by player 1): later steps are enqueued first
         int ring_idx = -1;         // ring entry of the gathered frame (page-locked ring), -1: a heap image
@@ -151,7 +153,10 @@ public:
     // &DepthFiller (the same for every member): after a step, the grids of the edge maps its callbacks get (edgehip_depth_fill on the old slot)
     bool dfill = false;
     edgehip_depth_fill_params dfp{};
-    int dfGrids(int slot, const std::vector<int32_t> &seq, std::vector<DepthGrid *> &dst);
+    edgehip_depth_surface_params dsp{};   // Surface / DenseImage (both 0: off)
+    // edgehip_depth_fill on `slot` (and edgehip_depth_surface when dsp is on), then the products of sequences seq[j] into dst[j], sdst[j], idst[j]
+    int dfGrids(int slot, const std::vector<int32_t> &seq, std::vector<DepthGrid *> &dst, std::vector<DepthSurface *> &sdst,
+                std::vector<DepthImage *> &idst);
     int cb_depth = 2;              // steps in flight when somebody has a callback (REBVO_GROUP_CB_DEPTH=1: the round-5 behaviour, A/B)
 
     void threadMain();
@@ -202,6 +207,9 @@ bool REBVO::groupAttach() {
         dfp.block_w = dfp.block_h = params.DF_BlockSize; dfp.iter_num = params.DF_IterNum; dfp.thresh_rel_rho = params.DF_ThreshRelRho;
         dfp.thresh_match_num = params.DF_ThreshMatchNum; dfp.bound_mode = params.DF_BoundMode; dfp.discard = params.DF_Discard;
     }
+    edgehip_depth_surface_params dsp;
+    std::memset(&dsp, 0, sizeof dsp);
+    if (dfill) { dsp.surface = params.DF_Surface != 0; dsp.image_mode = params.DF_DenseImage; }
     auto fail = [&](const std::string &msg) {
         last_error = msg;
         std::cout << last_error << "\n";
@@ -249,7 +257,9 @@ bool REBVO::groupAttach() {
         if (rc == 0) rc = edgehip_set_nav_log(g->hip, BatchGroup::kNavLog);
         g->dfill = dfill;
         g->dfp = dfp;
+        g->dsp = dsp;
         if (rc == 0 && dfill) rc = edgehip_depth_fill_enable(g->hip, &dfp);
+        if (rc == 0 && (dsp.surface || dsp.image_mode)) rc = edgehip_depth_surface_enable(g->hip, &dsp);
         g->frame_bytes = (size_t)params.ImageSize.w * params.ImageSize.h * sizeof(RGB24Pixel);
         void *ringp = nullptr;
         if (rc == 0 && edgehip_alloc_pinned(g->frame_bytes * CCAMBUFSIZE * want, &ringp) == 0) g->ring = static_cast<uint8_t *>(ringp);
@@ -287,6 +297,8 @@ bool REBVO::groupAttach() {
             return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same StereoAvaiable and the same &Stereo intrinsics");
         if (g->dfill != dfill || (dfill && std::memcmp(&g->dfp, &dfp, sizeof dfp) != 0))
             return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same &DepthFiller parameters");
+        if (std::memcmp(&g->dsp, &dsp, sizeof dsp) != 0)
+            return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same &DepthFiller Surface and DenseImage");
     }
     std::unique_lock<std::mutex> lk(g->mut);
     if (g->started && g->attached >= g->cap) {
@@ -688,8 +700,14 @@ int REBVO::BatchGroup::launch(long step, const std::vector<double> &ts) {
             ex.fetched = false;
             if (dfill) {   // the grids of the same edge maps (the old slot), read back now: the next step's fill reuses the device grids
                 std::vector<DepthGrid *> dst;
-                for (int seat : ex.seats) dst.push_back(&seats[seat].df_of[step & 3]);
-                rc = dfGrids((edgehip_cur_slot(hip) + 2) % 3, ex.seats, dst);
+                std::vector<DepthSurface *> sdst;
+                std::vector<DepthImage *> idst;
+                for (int seat : ex.seats) {
+                    dst.push_back(&seats[seat].df_of[step & 3]);
+                    sdst.push_back(&seats[seat].ds_of[step & 3]);
+                    idst.push_back(&seats[seat].di_of[step & 3]);
+                }
+                rc = dfGrids((edgehip_cur_slot(hip) + 2) % 3, ex.seats, dst, sdst, idst);
                 if (rc != 0) return rc;
             }
         }
@@ -699,12 +717,39 @@ int REBVO::BatchGroup::launch(long step, const std::vector<double> &ts) {
     return 0;
 }
 
-// edgehip_depth_fill on `slot` for all sequences, then the grids of sequences seq[j] into dst[j] (synchronises)
-int REBVO::BatchGroup::dfGrids(int slot, const std::vector<int32_t> &seq, std::vector<DepthGrid *> &dst) {
+// edgehip_depth_fill on `slot` for all sequences (and edgehip_depth_surface), then the grids of sequences seq[j] into dst[j] and their
+// surfaces / images into sdst[j] / idst[j] when those are on (synchronises)
+int REBVO::BatchGroup::dfGrids(int slot, const std::vector<int32_t> &seq, std::vector<DepthGrid *> &dst, std::vector<DepthSurface *> &sdst,
+                               std::vector<DepthImage *> &idst) {
     int rc = edgehip_depth_fill(hip, slot);
     int32_t gw = 0, gh = 0;
     if (rc == 0) rc = edgehip_depth_fill_size(hip, &gw, &gh);
+    if (rc == 0 && (dsp.surface || dsp.image_mode)) rc = edgehip_depth_surface(hip);
     if (rc != 0) return rc;
+    const size_t G = (size_t)gw * gh, N = (size_t)hp.w * hp.h, n = seq.size();
+    if (dsp.surface) {
+        std::vector<double *> pt(n), nm(n), di(n), md(n);
+        std::vector<float *> ar(n);
+        for (size_t j = 0; j < n; j++) {
+            DepthSurface &d = *sdst[j];
+            d.gw = gw; d.gh = gh;
+            d.point.resize(3 * G); d.normal.resize(3 * G); d.dist.resize(G); d.area.resize(G);
+            pt[j] = d.point.data(); nm[j] = d.normal.data(); di[j] = d.dist.data(); ar[j] = d.area.data(); md[j] = &d.min_dist;
+        }
+        rc = edgehip_download_depth_surfaces_batch(hip, (int)n, seq.data(), pt.data(), nm.data(), ar.data(), di.data(), md.data());
+        if (rc != 0) return rc;
+    }
+    if (dsp.image_mode) {
+        std::vector<float *> r(n), s(n);
+        for (size_t j = 0; j < n; j++) {
+            DepthImage &d = *idst[j];
+            d.w = hp.w; d.h = hp.h; d.mode = dsp.image_mode;
+            d.rho.resize(N); d.s_rho.resize(N);
+            r[j] = d.rho.data(); s[j] = d.s_rho.data();
+        }
+        rc = edgehip_download_depth_images_batch(hip, (int)n, seq.data(), r.data(), s.data());
+        if (rc != 0) return rc;
+    }
     std::vector<double *> r(seq.size()), s(seq.size());
     std::vector<uint8_t *> f(seq.size());
     for (size_t j = 0; j < seq.size(); j++) {
@@ -796,11 +841,25 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
             PipeBuffer &ob = cf->pipe.RequestBuffer(1);
             deliver[i] = &ob;
             ob.depth_grid = nullptr;
+            ob.depth_surface = nullptr;
+            ob.depth_image = nullptr;
             if (dfill && cf->haveCallBack() && cb_depth > 1 && in_export(i)) {   // the grid of exactly the lists exported with this step
                 std::unique_ptr<DepthGrid> &gd = cf->df_grids[&ob];
                 if (!gd) gd.reset(new DepthGrid);
                 std::swap(*gd, st.df_of[step & 3]);
                 ob.depth_grid = gd.get();
+                if (dsp.surface) {
+                    std::unique_ptr<DepthSurface> &sd = cf->df_surfs[&ob];
+                    if (!sd) sd.reset(new DepthSurface);
+                    std::swap(*sd, st.ds_of[step & 3]);
+                    ob.depth_surface = sd.get();
+                }
+                if (dsp.image_mode) {
+                    std::unique_ptr<DepthImage> &id = cf->df_images[&ob];
+                    if (!id) id.reset(new DepthImage);
+                    std::swap(*id, st.di_of[step & 3]);
+                    ob.depth_image = id.get();
+                }
             }
             if (cf->haveCallBack() && cb_depth > 1) {
                 // the lists were packed behind this step (launch()); a callback registered after that gets this one delivery without
@@ -826,13 +885,26 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
         for (size_t j = 0; j < cb_buf.size(); j++) cb_buf[j]->ef->kn = rc == 0 ? kn[j] : 0;
         if (rc == 0 && dfill) {   // the grids of the same lists
             std::vector<DepthGrid *> dst;
+            std::vector<DepthSurface *> sdst;
+            std::vector<DepthImage *> idst;
             for (size_t j = 0; j < cb_buf.size(); j++) {
-                std::unique_ptr<DepthGrid> &gd = seats[cb_seq[j]].cf->df_grids[cb_buf[j]];
+                REBVO *cf = seats[cb_seq[j]].cf;
+                std::unique_ptr<DepthGrid> &gd = cf->df_grids[cb_buf[j]];
                 if (!gd) gd.reset(new DepthGrid);
                 dst.push_back(gd.get());
+                std::unique_ptr<DepthSurface> &sd = cf->df_surfs[cb_buf[j]];
+                if (!sd) sd.reset(new DepthSurface);
+                sdst.push_back(sd.get());
+                std::unique_ptr<DepthImage> &id = cf->df_images[cb_buf[j]];
+                if (!id) id.reset(new DepthImage);
+                idst.push_back(id.get());
             }
-            rc = dfGrids(slot_before, cb_seq, dst);
-            for (size_t j = 0; j < cb_buf.size(); j++) cb_buf[j]->depth_grid = rc == 0 ? dst[j] : nullptr;
+            rc = dfGrids(slot_before, cb_seq, dst, sdst, idst);
+            for (size_t j = 0; j < cb_buf.size(); j++) {
+                cb_buf[j]->depth_grid = rc == 0 ? dst[j] : nullptr;
+                cb_buf[j]->depth_surface = rc == 0 && dsp.surface ? sdst[j] : nullptr;
+                cb_buf[j]->depth_image = rc == 0 && dsp.image_mode ? idst[j] : nullptr;
+            }
         }
     }
     if (have_ex) {
@@ -1068,6 +1140,36 @@ extern "C" int rebvo_group_depth_fill_selftest(const char *config_file) {
     if (d.Init() || d.lastError().find("DepthFiller") == std::string::npos) return 5;
     REBVO e(p);
     if (!e.Init()) return 6;                                                              // the same parameters: the group starts
+    a.CleanUp();
+    e.CleanUp();
+    return 0;
+}
+
+// Members of one group with other &DepthFiller Surface / DenseImage keys are refused at Init() (GPU test hook beside
+// rebvo_group_depth_fill_selftest): 0 = as expected
+extern "C" int rebvo_group_depth_surface_selftest(const char *config_file) {
+    using namespace rebvo;
+    REBVO proto(config_file);
+    if (!proto.isInitOk()) return 1;
+    REBVOParameters p = proto.getParams();
+    p.CameraType = 3; p.ImuMode = 0; p.StereoAvaiable = false;
+    p.GpuBatchGroup = "ds_selftest";
+    p.GpuBatchSize = 2;
+    p.DF_BlockSize = 10;
+    p.DF_Surface = 1;
+    p.DF_DenseImage = 1;
+    REBVO a(p);
+    if (!a.Init()) return 2;
+    REBVOParameters q = p;
+    q.DF_Surface = 0;
+    REBVO b(q);
+    if (b.Init() || b.lastError().find("Surface") == std::string::npos) return 3;   // surface off beside surface on
+    q = p;
+    q.DF_DenseImage = 2;
+    REBVO c(q);
+    if (c.Init() || c.lastError().find("DenseImage") == std::string::npos) return 4;   // another image mode
+    REBVO e(p);
+    if (!e.Init()) return 5;                                                          // the same keys: the group starts
     a.CleanUp();
     e.CleanUp();
     return 0;

@@ -311,6 +311,8 @@ REBVO::REBVO(const char *configFile)
     config.get("DepthFiller", "IterNum", p.DF_IterNum, false);
     config.get("DepthFiller", "BoundMode", p.DF_BoundMode, false);
     config.get("DepthFiller", "Discard", p.DF_Discard, false);
+    config.get("DepthFiller", "Surface", p.DF_Surface, false);
+    config.get("DepthFiller", "DenseImage", p.DF_DenseImage, false);
     construct();
 }
 
