@@ -245,7 +245,9 @@ int edgehip_minimizer_rv(edgehip_ctx *ctx, int slot_new, int slot_old);
  * as T (P0, the transformed points, residuals, gradients, Jacobian rows, the 28 sums, JtJ / JtF / h / X) is then computed and rounded in
  * float; the uncertainty gate, q_rho, the 6x6 solves and the Levenberg-Marquardt scalars stay double, as there.  Results follow the
  * reference's float instantiation to float accuracy (the 28 float sums are added in another tree than PairWiseVAdd<float>):
- * tests/test_tracker_f32_gpu.py states the tolerance.  The depth filter, the matcher and the detector are not affected.  ImuMode 0 only. */
+ * tests/test_tracker_f32_gpu.py states the tolerance.  The depth filter, the matcher and the detector are not affected.  ImuMode 0 without
+ * a stereo rig only, in either order: 32 is refused (EDGEHIP_ERR_STATE) after edgehip_imu_enable / edgehip_set_stereo_rig, and those two
+ * are refused while the precision is 32 (nothing changes; set 64 first). */
 int edgehip_set_tracker_precision(edgehip_ctx *ctx, int bits);
 /* The 6x6 solve between two evaluations, n independent systems (A [n][36] row-major, b [n][6], h [n][6], host pointers):
  * svd_rule = 0: h = TooN::Cholesky<6>(A).backsub(b) (global_tracker.cpp:767-768); svd_rule = 1: h = TooN::SVD<>(A).backsub(b) with

@@ -85,3 +85,89 @@ def teacher_forced_replay(eh, orc, frame_of, nframes, dt=0.05, forced=True, tol_
     out["max_dV"] = float(max(out["dV"]))
     out["max_dW"] = float(max(out["dW"]))
     return out
+
+
+def _so3_exp(w):
+    w = np.asarray(w, np.float64)
+    th = np.linalg.norm(w)
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    if th < 1e-9:
+        return np.eye(3) + K
+    return np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th ** 2 * (K @ K)
+
+
+def rerun_directed_matching(p, old, mask_old, retuned_old, st, img, V, RVel, W):
+    """The reference's matching of one frame, from the state it carried into the frame (`old`: the previous edge map, `st`: its
+    SeqState) but with a GIVEN tracker result: stage A, field, Minimizer_RV (for the forward matches it leaves), FordwardMatch,
+    rotate_keylines(exp(W)), directed_matching(V, RVel) — the sequence of rebvo_second_t.cpp:172-410.  Returns m_id of the new edge
+    map.  With the reference's own V / RVel / W this reproduces its frame; with the device's it says which matches follow from the
+    last bits of the device's pose alone (a KeyLine `attributed` to them)."""
+    orc = _o.Oracle("ref", p)
+    try:
+        orc.set_keylines(0, old, mask_old, retuned_old)
+        orc.stage_a(1, img, st.tresh, st.l_kl_num)
+        orc.build_field(1, p.search_range, orc.retuned(1))
+        q = orc.quantile(0, pct=p.qcut_quantile, n=p.qcut_nbins)
+        orc.minimizer_rv(1, 0, st.V[:], st.W[:], p.tracker_match_thresh, p.tracker_iter_num, p.tracker_init_type, p.reweight_distance,
+                         q, p.match_num_thresh, p.tracker_init_iter_num)
+        orc.forward_match(0, 1)
+        R0 = _so3_exp(W)
+        orc.rotate_keylines(0, R0)
+        orc.directed_matching(1, 0, np.asarray(V, np.float64), np.asarray(RVel, np.float64).reshape(3, 3), R0.T, p.match_thresh_module,
+                              p.match_thresh_angle, p.search_range, p.loc_unc_match)
+        return orc.keylines(1)["m_id"].copy()
+    finally:
+        orc.close()
+
+
+def teacher_forced_batch(eh, orcs, seqs, frame_of, nframes, dt=0.05, forced=True, tol_rel=1e-6, tol_abs=1e-9, check=None):
+    """teacher_forced_replay for a whole batch: `eh` runs nseq sequences (frame_of(k) -> their frames [nseq, h, w, 3]); sequence
+    seqs[j] of them is followed by its own reference orcs[j], whose state is injected into it before every frame (forced), while
+    the rest of the batch runs free around them.  check(k, j, nav_dev, nav_ref, pre): called after every frame for every checked
+    sequence, while device and reference still hold the frame (pre: dict(old, mask_old, retuned_old, state, img) = what the
+    reference carried into the frame).
+
+    Returns one teacher_forced_replay-style dict per checked sequence."""
+    outs = [{"seq": int(s), "forced": bool(forced), "dV": [], "dW": [], "outside_tolerance": [], "knife_edge_frames": []} for s in seqs]
+    for k in range(nframes):
+        batch = frame_of(k)
+        pres = []
+        for j, (s, orc) in enumerate(zip(seqs, orcs)):
+            so = orc.cur_slot()
+            pres.append(dict(old=orc.keylines(so).copy(), mask_old=orc.mask(so), retuned_old=orc.retuned(so), state=orc.seq_state(),
+                             img=batch[s]) if k else None)
+            if forced and k:
+                inject_reference_state(eh, orc, s)
+        eh.upload_rgb(eh.next_slot(), batch)
+        eh.process_frame(dt * k)
+        navs = eh.read_nav()
+        for j, (s, orc) in enumerate(zip(seqs, orcs)):
+            out, ng = outs[j], navs[s]
+            _, nr = orc.process_frame(batch[s], dt * k)
+            if k == 0:
+                out["dV"].append(0.0)
+                out["dW"].append(0.0)
+                if ng.kn != nr.kn:
+                    out["outside_tolerance"].append({"frame": 0, "kn": [int(ng.kn), int(nr.kn)]})
+            else:
+                p = orc.p
+                amb = _o.half_pixel_keylines(pres[j]["old"], orc.field(orc.cur_slot())[:, :, 1], p.ppx, p.ppy, nr.s_rho_q, p.w, p.h)
+                if amb:
+                    out["knife_edge_frames"].append({"frame": k, "keylines": [i for i, _ in amb[:8]]})
+                step = float(np.linalg.norm(nr.V[:]) + np.linalg.norm(nr.W[:]))
+                fin = bool(np.all(np.isfinite(nr.V[:])) and np.all(np.isfinite(nr.W[:])))
+                dv = float(np.max(np.abs(np.array(ng.V[:]) - np.array(nr.V[:])))) if fin else 0.0
+                dw = float(np.max(np.abs(np.array(ng.W[:]) - np.array(nr.W[:])))) if fin else 0.0
+                out["dV"].append(dv)
+                out["dW"].append(dw)
+                counts_dev = (int(ng.kn), int(ng.estimation_ok), int(ng.klm_num))
+                counts_ref = (int(nr.kn), int(nr.estimation_ok), int(nr.klm_num))
+                tol = tol_rel * step + tol_abs
+                if counts_dev != counts_ref or dv > tol or dw > tol or ng.tresh != nr.tresh:
+                    out["outside_tolerance"].append({"frame": k, "dV": dv, "dW": dw, "tolerance": tol, "tresh": [ng.tresh, nr.tresh],
+                                                     "kn_ok_klm": [list(counts_dev), list(counts_ref)], "knife_edge": bool(amb)})
+            if check is not None:
+                check(k, j, ng, nr, pres[j])
+    for out in outs:
+        out["max_dV"], out["max_dW"] = float(max(out["dV"])), float(max(out["dW"]))
+    return outs

@@ -985,6 +985,14 @@ __device__ __forceinline__ void tvr_body(const TvrArgs &a, const int seq, const 
             }
             fs = fm * inv_q;
 #endif
+        } else if (!REWEIGHT && !KF && ikl < kn && s_rho == 0) {
+            // (as in tvr2_body: the reference's 0 / 0 for a skipped KeyLine with s_rho = 0, global_tracker.cpp:456-461, :507)
+            const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+            if (PROCJF) {
+#pragma unroll
+                for (int j = 0; j < 6; j++) J[j] = qnan;
+            }
+            fs = qnan;
         }
         if (GRAM_MFMA) {
             // the KeyLine's row (J0..J5, fm, 0) for the Gram matrix below; rows of skipped / absent KeyLines are zero
@@ -1505,6 +1513,15 @@ __device__ __forceinline__ void tvr2_body(const TvrArgs &a, const int seq, const
 #else
             fmc[c] *= inv_q;
 #endif
+        } else if (ikl < kn && s_rho == 0) {
+            // the reference divides a skipped KeyLine's zero row by q_rho = s_rho all the same (global_tracker.cpp:456-461, :507):
+            // 0 / 0, and every sum of the evaluation is NaN (its initialisation chains then reject every step)
+            const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+            if (PROCJF) {
+#pragma unroll
+                for (int j = 0; j < 6; j++) J[j] = qnan;
+            }
+            fmc[c] = qnan;
         }
     }
 #if EDGEHIP_TVR2_PARK

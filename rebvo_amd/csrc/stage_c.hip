@@ -1658,6 +1658,7 @@ int edgehip_set_stereo_rig(edgehip_ctx *c, int slot_pair, const double *t, const
         set_error("set_stereo_rig: the pair slot is the last of at least three slots");
         return EDGEHIP_ERR_ARG;
     }
+    if (c->tracker_f32) { set_error("set_stereo_rig: the float tracker is Minimizer_RV<float> (no stereo rig): edgehip_set_tracker_precision(ctx, 64) first"); return EDGEHIP_ERR_STATE; }
     if (c->frames_seen != 0) { set_error("set_stereo_rig: set the rig before the first frame (or after edgehip_reset)"); return EDGEHIP_ERR_STATE; }
     c->rig.enabled = true;
     c->rig.slot_pair = slot_pair;

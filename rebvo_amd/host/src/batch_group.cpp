@@ -216,6 +216,8 @@ bool REBVO::groupAttach() {
         return false;
     };
     if (want < 1) return fail("REBVO(hip): &GPU BatchGroup needs BatchSize >= 1 (the number of objects that share the context)");
+    if (params.GpuTrackerPrecision == 32 && (imu_mode || stereo))   // (edgehip_imu_enable / edgehip_set_stereo_rig refuse it too)
+        return fail("REBVO(hip): &GPU TrackerPrecision=32 is Minimizer_RV<float>, the tracker of ImuMode 0 without a stereo pair");
     std::unique_lock<std::mutex> reg(BatchGroup::regMutex());
     BatchGroup *g = nullptr;
     if (named) {

@@ -444,13 +444,23 @@ bool REBVO::Init() {
         dscam_pair = nullptr;
         return false;
     }
+    if (params.GpuTrackerPrecision == 32 && (params.ImuMode > 0 || params.StereoAvaiable)) {
+        // (the host-driven IMU branch never enables the device's, so edgehip_set_tracker_precision would not see it)
+        last_error = "REBVO(hip): &GPU TrackerPrecision=32 is Minimizer_RV<float>, the tracker of ImuMode 0 without a stereo pair";
+        std::cout << last_error << "\n";
+        delete dscam;
+        dscam = nullptr;
+        delete dscam_pair;
+        dscam_pair = nullptr;
+        return false;
+    }
     if (params.ImuMode > 0) imuTrackInit();
     edgehip_params hp;
     fill_hip_params(params, hp);
     hp.stereo_available = params.StereoAvaiable ? 1 : 0;
     // ring of 3 frame slots; with a stereo pair one more slot, behind the ring, holds the pair image's edge map
     int rc = edgehip_create(&hp, 1, params.StereoAvaiable ? 4 : 3, params.GpuDevice, &hip);
-    if (rc == 0 && params.GpuTrackerPrecision != 64) rc = edgehip_set_tracker_precision(hip, params.GpuTrackerPrecision);   // (refused with ImuMode > 0 / a stereo rig)
+    if (rc == 0 && params.GpuTrackerPrecision != 64) rc = edgehip_set_tracker_precision(hip, params.GpuTrackerPrecision);
     if (rc == 0 && params.StereoAvaiable) {
         // search radius 100 (rebvo_second_t.cpp:473); with the IMU branch the host drives the stereo stages itself
         rc = edgehip_set_slot_camera(hip, 3, params.pp_x_stereo, params.pp_y_stereo, params.z_f_x_stereo, params.z_f_y_stereo);

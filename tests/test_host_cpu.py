@@ -82,6 +82,18 @@ def test_imu_config_errors(exe, tmp_path):
     assert "Loaded 2 datums" in r.stdout and r.returncode in (0, 4)
 
 
+def test_float_tracker_with_imu_is_refused(exe, tmp_path):
+    """&GPU TrackerPrecision=32 is Minimizer_RV<float>, the ImuMode 0 tracker: together with ImuMode > 0 Init() refuses the
+    configuration before it asks for a device (the same message with or without a GPU)."""
+    cfg = tmp_path / "cfg"
+    p = edgehip.euroc_params(376, 240)
+    imu_csv = tmp_path / "imu.csv"
+    imu_csv.write_text("#t,gx,gy,gz,ax,ay,az\n1.0,0,0,0,0,9.8,0\n1.01,0,0,0,0,9.8,0\n")
+    write_global_config(cfg, p, imu=dict(mode=2, file=str(imu_csv), time_scale=1), gpu=dict(tracker_precision=32))
+    r = _run(cfg, "/dev/null", 0, 1.0, 0.05)
+    assert r.returncode == 4 and "TrackerPrecision=32" in r.stdout, (r.returncode, r.stdout[-400:])
+
+
 def test_stereo_config_errors(exe, tmp_path):
     """StereoAvaiable makes the pair camera's list and the &Stereo intrinsics mandatory (src/rebvo/rebvo.cpp:195-216)."""
     cfg = tmp_path / "cfg"

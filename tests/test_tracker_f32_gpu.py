@@ -147,3 +147,21 @@ def test_precision_switch_rules():
     assert eh.lib.edgehip_set_tracker_precision(eh.ctx, 32) != 0      # Minimizer_RV<float> is the ImuMode 0 tracker
     assert eh.lib.edgehip_set_tracker_precision(eh.ctx, 64) == 0
     eh.close()
+    # the reverse order: the float tracker first, then the IMU branch or a stereo rig — refused, and nothing changes
+    eh = edgehip.EdgeHip(edgehip.euroc_params(376, 240, stereo_available=1), nseq=1, nslots=4)
+    eh.set_tracker_precision(32)
+    ip = edgehip.euroc_imu_params()
+    assert eh.lib.edgehip_imu_enable(eh.ctx, C.byref(ip)) != 0
+    assert b"float tracker" in eh.lib.edgehip_last_error()
+    t, R = np.array([0.11, 0.0, 0.0]), np.eye(3).ravel().copy()
+    dp = C.POINTER(C.c_double)
+    assert eh.lib.edgehip_set_stereo_rig(eh.ctx, 3, t.ctypes.data_as(dp), R.ctypes.data_as(dp), C.c_double(100.0)) != 0
+    assert b"float tracker" in eh.lib.edgehip_last_error()
+    assert eh.lib.edgehip_set_tracker_precision(eh.ctx, 32) == 0       # still neither IMU nor rig: 32 stays legal
+    eh.set_tracker_precision(64)                                       # back to 64 bits: both are accepted
+    eh.set_stereo_rig(3, t, R)
+    assert eh.lib.edgehip_set_tracker_precision(eh.ctx, 32) != 0
+    eh.set_stereo_rig(-1)
+    eh.imu_enable(ip)
+    assert eh.lib.edgehip_set_tracker_precision(eh.ctx, 32) != 0
+    eh.close()
