@@ -547,6 +547,66 @@ int edgehip_download_depth_images_batch(edgehip_ctx *ctx, int n, const int32_t *
  * (either may be NULL; e.g. torch tensors), without a host bounce — like edgehip_read_nav_log_device.  The copy is complete on return. */
 int edgehip_depth_image_device(edgehip_ctx *ctx, int first, int count, float *rho_dev, float *s_rho_dev);
 
+/* ---- cross-view surface integration (the key-frame viewer's OcGrid ray cut) ---------------------------------------------
+ * Which cells of several filled grids are occluded: a cell is hidden when it lies in free space that another view's rays have crossed
+ * (src/visualizer/surface_integrator.cpp, driven by app/kf_visualizer/main.cpp:110-116, 192, 201).  A "view" is what the reference
+ * takes from a keyframe there: its depth_filler grid (rho, s_rho), Pose (3x3, row-major), Pos and scale K, with
+ * Local2WorldScaled(p) = Pose * p * K + Pos (include/mtracklib/keyframe.h:101-103); camera and block size are the context's.
+ * The reference registers every cell in the voxels its surface samples fall in (OcGrid::fillKFList, :167-229), then marches a ray per
+ * cell of each casting view from the camera centre to the cell's point at rho + s_rho in steps of the smallest voxel edge, and clears
+ * the `visibility` of every registered cell of ANOTHER view in each voxel it steps through (rayCutSurface / hideAll, :235-266,
+ * :153-163).  Visibility only falls, so the result does not depend on the order: cell c of view A ends hidden iff some voxel holds
+ * both a fill sample of c and a ray step of a casting view B != A.  The device keeps one 4-byte word per voxel (which views' rays
+ * crossed it: none, exactly one and which, or several) instead of the reference's per-voxel pointer lists, marks the rays, then walks
+ * every cell's samples in the reference's order and arithmetic (float accumulators with double increments; getImg3DPos's float
+ * bilinear rho, depth_filler.h:133-163; fp64 elsewhere) and looks them up.  Every flag equals the reference's
+ * (tests/surface_integrate_port.py restates it).  Up to 1024 views.  Departures, all where the reference has no defined result:
+ *   - a fill sample or ray step outside the box is dropped: outside = a quotient (p - origin)[i] / block[i] that is negative, not
+ *     finite or >= n on any axis.  (The reference converts negative doubles to u_int and indexes with the wrapped value, and lets
+ *     p - origin == size through.)  A ray stops at the first step from which every later step is outside as well.
+ *   - a cell whose rho / K is not finite or not positive contributes no fill samples (it stays visible; its ray is still cast).  The
+ *     reference's sample loop does not end when its step is 0; neither does it when an accumulator stops advancing (a step below half
+ *     an ulp of the pixel coordinate): the walk ends there.
+ *   - a ray whose length / step is not finite, or is past the int range, takes no steps (the x86 conversion gives INT_MIN there: the
+ *     same).  rho + s_rho == 0 is such a ray.
+ *   - the box needs a finite origin and a finite, positive size (EDGEHIP_ERR_ARG otherwise).
+ *   - fillKFList's "blocks filled" counter is not produced. */
+typedef struct edgehip_surface_views_params {
+    int32_t capacity;       /* view slots, 1..1024 */
+    int32_t nx, ny, nz;     /* OcGrid's grid_size (main.cpp:113 uses 500, 500, 500) */
+} edgehip_surface_views_params;
+/* Allocates the view store (per slot: the two grids, the pose, one visibility byte per cell: 17 B per cell) and the voxel plane
+ * (4 B per voxel: 500 MB at 500^3).  params == NULL frees them.  EDGEHIP_ERR_STATE while the depth fill is off, EDGEHIP_ERR_ARG for a
+ * capacity outside [1, 1024] or a dimension < 1, EDGEHIP_ERR_MEMORY when the allocation fails (the store is then off; the context
+ * stays usable).  Disabling the fill, or enabling it with other block sizes, frees the store too. */
+int edgehip_surface_views_enable(edgehip_ctx *ctx, const edgehip_surface_views_params *params);
+/* Sequence `seq`'s grid of the last edgehip_depth_fill into slot `view`, with the pose the caller tracks for it (what edgehip_nav
+ * reports: Pose[9] row-major, Pos[3], K), in-stream: keyframe + initDepthFiller (keyframe.cpp:171-184) as the integrator sees them.
+ * Sets the view's visibility to 1 (depth_filler::ResetVisibility, depth_filler.cpp:190-194).  EDGEHIP_ERR_STATE before the first fill. */
+int edgehip_surface_view_capture(edgehip_ctx *ctx, int seq, int view, const double *Pose, const double *Pos, double K);
+/* The same from host arrays rho[gh*gw], s_rho[gh*gw] (key frames loaded from a file, keyframe::loadKeyframesFromFile, main.cpp:82;
+ * stage-isolated tests).  The arrays are free on return. */
+int edgehip_surface_view_upload(edgehip_ctx *ctx, int view, const double *rho, const double *s_rho, const double *Pose, const double *Pos,
+                                double K);
+/* Empties slot `view`: like a key frame without a depth filler (depthFillerAval() false, :42, :173, :237) it casts no rays, is not
+ * tested and does not count in edgehip_surface_space. */
+int edgehip_surface_view_clear(edgehip_ctx *ctx, int view);
+/* SurfaceInt::analizeSpaceSize over the stored views (surface_integrator.cpp:32-68): origin[3] = the minimum and size[3] = maximum -
+ * minimum of Local2WorldScaled(get3DPos(x, y)) over every cell, bit for bit (the maxima start at 1e-20 as there), except the sign of a
+ * zero.  Synchronises. */
+int edgehip_surface_space(edgehip_ctx *ctx, double *origin, double *size);
+/* OcGrid(origin, size, {nx, ny, nz}) + fillKFList + rayCutSurface (surface_integrator.cpp:120-132, 167-229, 235-266), in-stream: clears
+ * the voxel plane, marks the rays of cast_views[n_cast] (NULL: every stored view, main.cpp:192; empty slots in the list are skipped),
+ * then tests every cell of every stored view.  accumulate == 0 sets every visibility to 1 first (ResetVisibility); accumulate != 0
+ * keeps earlier hides (main.cpp:201's single-view cut after :192).  origin and size are the caller's: edgehip_surface_space's result
+ * for the reference's box (main.cpp:110-113), or a padded one that keeps the camera centres inside. */
+int edgehip_surface_integrate(edgehip_ctx *ctx, const double *origin, const double *size, int n_cast, const int32_t *cast_views,
+                              int accumulate);
+/* df_point::visibility of the cells of `view`: vis[gh*gw], 1 = visible, row-major.  Synchronises.  EDGEHIP_ERR_STATE for an empty slot. */
+int edgehip_download_surface_visibility(edgehip_ctx *ctx, int view, uint8_t *vis);
+/* The same for n slots views[n] (vis[j] per request; an entry may be NULL).  Synchronises once. */
+int edgehip_download_surface_visibilities_batch(edgehip_ctx *ctx, int n, const int32_t *views, uint8_t *const *vis);
+
 /* ---- measurement ------------------------------------------------------------------------------------- */
 /* Names of the kernel groups timed by the built-in HIP-event profiler, and their accumulated device time.
  * edgehip_profile_enable(ctx, 1) brackets every launch group with events on the context stream (adds host

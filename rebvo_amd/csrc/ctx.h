@@ -581,6 +581,9 @@ struct edgehip_ctx {
     // edgehip_depth_surface_enable: per-cell surface and per-pixel depth image from the fill's grids (depth_surface.hip); null when off
     struct DepthSurface;
     DepthSurface *dsurf = nullptr;
+    // edgehip_surface_views_enable: stored views (grid + pose) and the voxel plane of the cross-view surface integration (surface_integrate.hip); null when off
+    struct SurfaceViews;
+    SurfaceViews *sviews = nullptr;
 };
 
 namespace edgehip {
@@ -698,5 +701,6 @@ void depth_fill_free(edgehip_ctx *c);               // depth_fill.hip: edgehip_d
 int depth_fill_geometry(edgehip_ctx *c, int32_t *gw, int32_t *gh, int32_t *bw, int32_t *bh);   // depth_fill.hip: EDGEHIP_ERR_STATE when off
 bool depth_fill_grids(edgehip_ctx *c, const double **rho, const double **s_rho);   // depth_fill.hip: false before the first fill
 void depth_surface_free(edgehip_ctx *c);            // depth_surface.hip
+void surface_views_free(edgehip_ctx *c);            // surface_integrate.hip
 
 }  // namespace edgehip

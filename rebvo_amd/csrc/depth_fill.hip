@@ -282,6 +282,7 @@ static void depth_fill_release(edgehip_ctx *c) {
 
 void edgehip::depth_fill_free(edgehip_ctx *c) {
     depth_surface_free(c);
+    surface_views_free(c);
     depth_fill_release(c);
 }
 
@@ -308,7 +309,7 @@ int edgehip_depth_fill_enable(edgehip_ctx *c, const edgehip_depth_fill_params *p
     const int gw = c->plan.w / p->block_w, gh = c->plan.h / p->block_h;
     if (gw < 1 || gh < 1) { set_error("depth_fill_enable: the grid (image size / block size) is smaller than 1x1"); return EDGEHIP_ERR_ARG; }
     // the depth surface stays enabled while the blocks (and so the grid) stay the same; it reads the new grids after the next fill
-    if (c->dfill && (c->dfill->p.block_w != p->block_w || c->dfill->p.block_h != p->block_h)) depth_surface_free(c);
+    if (c->dfill && (c->dfill->p.block_w != p->block_w || c->dfill->p.block_h != p->block_h)) { depth_surface_free(c); surface_views_free(c); }
     depth_fill_release(c);
     auto *d = new edgehip_ctx::DepthFill;
     d->p = *p;
@@ -333,6 +334,7 @@ int edgehip_depth_fill_enable(edgehip_ctx *c, const edgehip_depth_fill_params *p
         (void)hipGetLastError();
         delete d;
         depth_surface_free(c);
+        surface_views_free(c);
         set_error("depth_fill_enable: device allocation failed");
         return EDGEHIP_ERR_MEMORY;
     }
@@ -353,6 +355,7 @@ int edgehip_depth_fill_enable(edgehip_ctx *c, const edgehip_depth_fill_params *p
         (void)hipFree(d->arena);
         delete d;
         depth_surface_free(c);
+        surface_views_free(c);
         set_error("depth_fill_enable: hipMemsetAsync failed");
         return EDGEHIP_ERR_DEVICE;
     }

@@ -199,6 +199,11 @@ class DepthSurfaceParams(C.Structure):
     _fields_ = [("surface", C.c_int32), ("image_mode", C.c_int32)]
 
 
+class SurfaceViewsParams(C.Structure):
+    """edgehip_surface_views_params: view slots and OcGrid's voxel dimensions."""
+    _fields_ = [("capacity", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32)]
+
+
 NAV_DTYPE = np.dtype(Nav)   # numpy view of edgehip_nav (same offsets as the ctypes struct)
 assert NAV_DTYPE.itemsize == C.sizeof(Nav)
 
@@ -222,6 +227,9 @@ EXPORTS = [
     "edgehip_download_depth_grids_batch",
     "edgehip_depth_surface_enable", "edgehip_depth_surface", "edgehip_download_depth_surface", "edgehip_download_depth_surfaces_batch",
     "edgehip_download_depth_image", "edgehip_download_depth_images_batch", "edgehip_depth_image_device",
+    "edgehip_surface_views_enable", "edgehip_surface_view_capture", "edgehip_surface_view_upload", "edgehip_surface_view_clear",
+    "edgehip_surface_space", "edgehip_surface_integrate", "edgehip_download_surface_visibility",
+    "edgehip_download_surface_visibilities_batch",
 ]
 
 _lib = None
@@ -750,6 +758,69 @@ class EdgeHip:
         self._ck(self.lib.edgehip_depth_image_device(self.ctx, int(first), int(count),
                                                      C.c_void_p(rho.data_ptr() if rho is not None else None),
                                                      C.c_void_p(s_rho.data_ptr() if s_rho is not None else None)))
+
+    # ---- cross-view surface integration (surface_integrator.cpp: analizeSpaceSize, OcGrid::fillKFList / rayCutSurface) ----
+    def surface_views_enable(self, capacity=64, n=(500, 500, 500)):
+        """edgehip_surface_views_enable: `capacity` view slots and an nx x ny x nz voxel plane; capacity=None frees them."""
+        if capacity is None:
+            self._ck(self.lib.edgehip_surface_views_enable(self.ctx, None))
+            return
+        nx, ny, nz = (int(n),) * 3 if np.isscalar(n) else (int(v) for v in n)
+        p = SurfaceViewsParams(int(capacity), nx, ny, nz)
+        self._ck(self.lib.edgehip_surface_views_enable(self.ctx, C.byref(p)))
+
+    @staticmethod
+    def _pose(Pose, Pos):
+        return np.ascontiguousarray(Pose, np.float64).reshape(9), np.ascontiguousarray(Pos, np.float64).reshape(3)
+
+    def surface_view_capture(self, seq, view, Pose, Pos, K):
+        """edgehip_surface_view_capture: sequence seq's grid of the last depth_fill into slot `view` (in-stream)."""
+        Pose, Pos = self._pose(Pose, Pos)
+        self._ck(self.lib.edgehip_surface_view_capture(self.ctx, int(seq), int(view), _dp(Pose), _dp(Pos), C.c_double(K)))
+
+    def surface_view_upload(self, view, rho, s_rho, Pose, Pos, K):
+        """edgehip_surface_view_upload: (gh, gw) float64 grids into slot `view`."""
+        gw, gh = self.depth_fill_size()
+        rho, s_rho = np.ascontiguousarray(rho, np.float64), np.ascontiguousarray(s_rho, np.float64)
+        assert rho.shape == (gh, gw) and s_rho.shape == (gh, gw), (rho.shape, s_rho.shape, (gh, gw))
+        Pose, Pos = self._pose(Pose, Pos)
+        self._ck(self.lib.edgehip_surface_view_upload(self.ctx, int(view), _dp(rho), _dp(s_rho), _dp(Pose), _dp(Pos), C.c_double(K)))
+
+    def surface_view_clear(self, view):
+        self._ck(self.lib.edgehip_surface_view_clear(self.ctx, int(view)))
+
+    def surface_space(self):
+        """edgehip_surface_space -> (origin[3], size[3]) of analizeSpaceSize over the stored views."""
+        origin, size = np.empty(3), np.empty(3)
+        self._ck(self.lib.edgehip_surface_space(self.ctx, _dp(origin), _dp(size)))
+        return origin, size
+
+    def surface_integrate(self, origin, size, cast_views=None, accumulate=False):
+        """edgehip_surface_integrate: rays of cast_views (None: every stored view), then the test of every stored view (in-stream)."""
+        origin, size = np.ascontiguousarray(origin, np.float64).reshape(3), np.ascontiguousarray(size, np.float64).reshape(3)
+        if cast_views is None:
+            n, ptr = 0, None
+        else:
+            cast = np.ascontiguousarray(cast_views, dtype=np.int32).reshape(-1)
+            n = len(cast)
+            if n == 0:
+                cast = np.zeros(1, np.int32)   # an empty list is not NULL ("every stored view")
+            ptr = cast.ctypes.data_as(C.c_void_p)
+        self._ck(self.lib.edgehip_surface_integrate(self.ctx, _dp(origin), _dp(size), n, ptr, int(bool(accumulate))))
+
+    def download_surface_visibility(self, views):
+        """edgehip_download_surface_visibility(_batch): one slot -> (gh, gw) bool array; a sequence of slots -> a list of them."""
+        gw, gh = self.depth_fill_size()
+        if np.isscalar(views):
+            vis = np.empty((gh, gw), np.uint8)
+            self._ck(self.lib.edgehip_download_surface_visibility(self.ctx, int(views), vis.ctypes.data_as(C.c_void_p)))
+            return vis.astype(bool)
+        views = np.ascontiguousarray(views, dtype=np.int32)
+        n = len(views)
+        out = [np.empty((gh, gw), np.uint8) for _ in range(n)]
+        pv = (C.c_void_p * n)(*[o.ctypes.data for o in out])
+        self._ck(self.lib.edgehip_download_surface_visibilities_batch(self.ctx, n, views.ctypes.data_as(C.c_void_p), pv))
+        return [o.astype(bool) for o in out]
 
     def upload_keylines(self, seq, slot, kl, mask=None, retuned=0.0):
         kl = np.ascontiguousarray(kl, dtype=KEYLINE_DTYPE)
