@@ -602,6 +602,25 @@ int edgehip_surface_space(edgehip_ctx *ctx, double *origin, double *size);
  * for the reference's box (main.cpp:110-113), or a padded one that keeps the camera centres inside. */
 int edgehip_surface_integrate(edgehip_ctx *ctx, const double *origin, const double *size, int n_cast, const int32_t *cast_views,
                               int accumulate);
+/* SurfaceInt::checkDFRayCrossExaustive(target, hidder) (surface_integrator.cpp:70-116) for n_pairs ordered pairs (targets[j], hidders[j]),
+ * in-stream, in one launch: the same question as the OcGrid cut without the box, the resolution or the voxel plane.  A cell of the
+ * target is hidden when some ray of the hidder (from its camera centre through one of its cells, both taken into the target's frame
+ * by keyframe::transformTo, keyframe.h:105-109) passes the cell's point closer than its bubble, norm(bw, bh) / zfm * K / rho (:79, :95,
+ * :98-100), and the cell lies on the ray in front of the hidder's surface: 0 < distance along the ray < dist (:101-102).  Every target
+ * cell is tested against every hidder ray, in the reference's fp64 operations and their order, so every flag equals the reference's
+ * (tests/surface_ray_cross_port.py restates it).  As there, `dist` is what keyframe::initDepthFiller leaves in the grid through
+ * computeDistance(Zeros) (keyframe.cpp:181, depth_filler.cpp:170-182): norm(get3DPos(x, y)), NOT multiplied by the hidder's K, while the
+ * distance along the ray is in scaled units.  Cells with a rho that is zero, negative or not finite, and rays without length, take the
+ * branch IEEE comparison gives them (false for a NaN), as in the reference.  Visibility only falls, so the reference's early exits
+ * change nothing and the pairs may run in any order.
+ *   targets == hidders == NULL with n_pairs < 0: every ordered pair t != h of stored views.  With lists, a pair that names an empty
+ *   slot is skipped (depthFillerAval() false, :73).  EDGEHIP_ERR_ARG for an id outside [0, capacity) and — the one departure — for a
+ *   pair with t == h: the reference's answer there is decided by the rounding of each cell's distance to its own ray.  EDGEHIP_ERR_STATE
+ *   before edgehip_surface_views_enable.  On an error nothing is changed.
+ *   accumulate == 0 sets every visibility to 1 first (ResetVisibility); accumulate != 0 keeps earlier hides, those of
+ *   edgehip_surface_integrate included.  The flags come back through the visibility downloads below.
+ * The voxel plane is not touched: nx = ny = nz = 1 in edgehip_surface_views_enable is a valid way to have the store for this check alone. */
+int edgehip_surface_ray_cross(edgehip_ctx *ctx, int n_pairs, const int32_t *targets, const int32_t *hidders, int accumulate);
 /* df_point::visibility of the cells of `view`: vis[gh*gw], 1 = visible, row-major.  Synchronises.  EDGEHIP_ERR_STATE for an empty slot. */
 int edgehip_download_surface_visibility(edgehip_ctx *ctx, int view, uint8_t *vis);
 /* The same for n slots views[n] (vis[j] per request; an entry may be NULL).  Synchronises once. */

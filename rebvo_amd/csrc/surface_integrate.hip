@@ -16,6 +16,8 @@
 // Whatever the order of arrival, the first step of the second distinct view sees the first one's id and sets bit 31 (from then on the
 // atomicMax changes nothing), so "word != 0 and (bit 31 or id != A + 1)" — the test for view A — does not depend on the order.  An
 // agent-scope load in front skips both atomics where the word already says so (every ray of a view starts in the camera's voxel).
+//   k_sv_ray_cross  SurfaceInt::checkDFRayCrossExaustive (:70-116): the same question without the voxel plane, every cell of a target
+//                view against every ray of a hidder view, many ordered pairs of views per launch (see the kernel).
 // fp64 as the reference uses it; '/' and sqrt are the compiler's correctly rounded operations; -ffp-contract=off keeps products and sums
 // separately rounded.
 #include "ctx.h"
@@ -234,6 +236,126 @@ __global__ __launch_bounds__(kSvThreads) void k_sv_test(SvStore st, SvGeom g, Sv
     vis[c] = accumulate ? (uint8_t)(vis[c] && !hidden) : (uint8_t)!hidden;
 }
 
+// SurfaceInt::checkDFRayCrossExaustive(target, hidder) (surface_integrator.cpp:70-116) for a list of ordered pairs of views.  A target
+// cell is hidden when some hidder ray passes it closer than the cell's bubble (norm((point - ray_orig) ^ ray_versor) < buble_size, :98-100)
+// and the cell lies in front of the hidder's surface on that ray (0 < (point - ray_orig) * ray_versor < dist, :101-102).  The reference
+// recomputes everything inside its four loops; what depends on the hidder cell alone (ray_versor, dist), on the pair alone (ray_orig) or
+// on the target cell alone (point, buble_size, point - ray_orig) is formed once here, by the same operations in the same order.
+//
+// blockIdx.x = pair, blockIdx.y = 256 target cells, one per thread, in registers.  The block builds the hidder's rays a tile of 256 at a
+// time in LDS (one ray per thread); every lane then reads the same ray, a broadcast.  Visibility only falls, so a lane that finds its
+// cell hidden, or found it hidden already (an earlier call under accumulate, or another pair of this launch: any 0 read here is a
+// final value), has nothing left to find: a wave leaves the ray loop when all its lanes are so, the block when all its waves are.
+//
+// The square root of :98 is taken only where it can decide: with n2 the squared norm, sqrt(n2) < b is certain when n2 < b * b * (1 - 1e-6)
+// and impossible when n2 > b * b * (1 + 1e-6) (sqrt is monotone and correctly rounded; the margins are ten orders of magnitude above
+// the rounding of b * b and of the root).  In between, for a NaN, and for every bubble that is not a positive number whose square is
+// far from the subnormals and from infinity, the reference's own comparison decides.
+struct SvRay { double v[3], dist; };
+constexpr int kSvRayCheck = 8;   // rays between two ballots
+
+// keyframe::transformTo (keyframe.h:105-109): kfto.Pose.T() * (Pose * p + Pos - kfto.Pos); TooN's products are a dot product per row
+// (of the transpose: per column), result = 0 and += in index order.
+__device__ __forceinline__ void sv_transform_to(const double *H, const double *T, const double p[3], double o[3]) {
+    double w[3];
+    for (int i = 0; i < 3; i++) {
+        double s = 0;
+        s += H[3 * i] * p[0];
+        s += H[3 * i + 1] * p[1];
+        s += H[3 * i + 2] * p[2];
+        w[i] = s + H[9 + i] - T[9 + i];
+    }
+    for (int i = 0; i < 3; i++) {
+        double s = 0;
+        s += T[i] * w[0];
+        s += T[3 + i] * w[1];
+        s += T[6 + i] * w[2];
+        o[i] = s;
+    }
+}
+
+__global__ __launch_bounds__(kSvThreads) void k_sv_ray_cross(SvStore st, SvGeom g, const int2 *pairs) {
+    __shared__ SvRay rays[kSvThreads];
+    __shared__ int wave_done[kSvThreads / 64];
+    const int G = g.gw * g.gh, tid = threadIdx.x, wave = tid >> 6;
+    const int t = pairs[blockIdx.x].x, h = pairs[blockIdx.x].y;
+    const int c = blockIdx.y * kSvThreads + tid;
+    const double *T = st.pose + (size_t)t * 13, *H = st.pose + (size_t)h * 13;
+    const double *rho_h = st.rho + (size_t)h * G;
+    uint8_t *vis = st.vis + (size_t)t * G;
+
+    const double zero[3] = {0, 0, 0};
+    double ro[3];
+    sv_transform_to(H, T, zero, ro);                 // ray_orig (:89)
+
+    // the target cell: point (:93), buble_size (:95, norm_size :79) and point - ray_orig
+    double d[3] = {0, 0, 0}, bub = 0, lo = -1.0, hi = INFINITY;
+    bool crossed = true;
+    if (c < G) {
+        const double r = st.rho[(size_t)t * G + c];
+        double P[3];
+        sv_cell_point(c % g.gw, c / g.gw, r, g, P);
+        const double norm_size = sqrt((double)(g.bw * g.bw + g.bh * g.bh)) / g.zfm * T[12];   // util::norm(int, int)
+        bub = norm_size / r;
+        for (int i = 0; i < 3; i++) d[i] = P[i] * T[12] - ro[i];
+        if (bub > 1e-140 && bub < 1e140) {
+            const double b2 = bub * bub;
+            lo = b2 * (1.0 - 1e-6);
+            hi = b2 * (1.0 + 1e-6);
+        }
+        crossed = vis[c] == 0;
+    }
+    const bool hidden_before = crossed;
+
+    bool done = __ballot(!crossed) == 0;
+    for (int tile = 0; tile < G; tile += kSvThreads) {
+        if ((tid & 63) == 0) wave_done[wave] = done;
+        __syncthreads();                             // the last tile's reads are over; the flags are there
+        bool all = true;
+        for (int k = 0; k < kSvThreads / 64; k++) all = all && wave_done[k];
+        if (all) break;
+        const int hc = tile + tid;
+        if (hc < G) {                                // the hidder's ray through cell hc: ray_pass (:90), ray_versor (:91), dist (depth_filler.cpp:175-177)
+            double P[3], S[3], rp[3], u[3];
+            sv_cell_point(hc % g.gw, hc / g.gw, rho_h[hc], g, P);
+            for (int i = 0; i < 3; i++) S[i] = P[i] * H[12];
+            sv_transform_to(H, T, S, rp);
+            for (int i = 0; i < 3; i++) u[i] = rp[i] - ro[i];
+            double nn = 0, pp = 0;
+            for (int i = 0; i < 3; i++) nn += u[i] * u[i];
+            const double inv = 1 / sqrt(nn);         // unit(v) = v * (1 / sqrt(v * v))
+            for (int i = 0; i < 3; i++) rays[tid].v[i] = u[i] * inv;
+            for (int i = 0; i < 3; i++) pp += P[i] * P[i];
+            rays[tid].dist = sqrt(pp);               // norm(get3DPos(x, y) - Zeros): not scaled by K
+        }
+        __syncthreads();
+        if (done) continue;
+        const int n = min(kSvThreads, G - tile);
+        for (int j0 = 0; j0 < n; j0 += kSvRayCheck) {
+            const int j1 = min(j0 + kSvRayCheck, n);
+            for (int j = j0; j < j1; j++) {
+                const double vx = rays[j].v[0], vy = rays[j].v[1], vz = rays[j].v[2];
+                const double cx = d[1] * vz - d[2] * vy, cy = d[2] * vx - d[0] * vz, cz = d[0] * vy - d[1] * vx;   // operator^
+                double n2 = 0;
+                n2 += cx * cx;
+                n2 += cy * cy;
+                n2 += cz * cz;
+                if (!(n2 > hi)) {
+                    if (n2 < lo || sqrt(n2) < bub) {
+                        double along = 0;
+                        along += d[0] * vx;
+                        along += d[1] * vy;
+                        along += d[2] * vz;
+                        if (along > 0 && along < rays[j].dist) crossed = true;
+                    }
+                }
+            }
+            if (__ballot(!crossed) == 0) { done = true; break; }
+        }
+    }
+    if (crossed && !hidden_before) vis[c] = 0;       // visibility = false (:109-110); nothing sets it back
+}
+
 struct SvPose { double m[13]; };
 // a view's pose, and ResetVisibility (depth_filler.cpp:190-194) for its cells
 __global__ __launch_bounds__(kSvThreads) void k_sv_set_view(double *pose, uint8_t *vis, int G, SvPose p) {
@@ -254,6 +376,8 @@ struct edgehip_ctx::SurfaceViews {
     double *rho, *s_rho, *pose, *part;
     uint8_t *vis;
     unsigned *plane = nullptr;   // [nz][ny][nx] voxel words
+    int2 *pairs = nullptr;       // edgehip_surface_ray_cross's (target, hidder) list; grows on demand
+    size_t pairs_cap = 0;
     SvMask stored;
 };
 
@@ -262,6 +386,7 @@ void edgehip::surface_views_free(edgehip_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->sviews->arena) (void)hipFree(c->sviews->arena);
     if (c->sviews->plane) (void)hipFree(c->sviews->plane);
+    if (c->sviews->pairs) (void)hipFree(c->sviews->pairs);
     delete c->sviews;
     c->sviews = nullptr;
 }
@@ -437,6 +562,51 @@ int edgehip_surface_integrate(edgehip_ctx *c, const double *origin, const double
     hipLaunchKernelGGL(k_sv_rays, grid, dim3(kSvThreads), 0, c->stream, sv_store(c), sv_geom(c), b, cast, v->plane);
     EH_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_sv_test, grid, dim3(kSvThreads), 0, c->stream, sv_store(c), sv_geom(c), b, v->stored, (const unsigned *)v->plane, accumulate);
+    EH_LAUNCH_CHECK();
+    return 0;
+}
+
+int edgehip_surface_ray_cross(edgehip_ctx *c, int n_pairs, const int32_t *targets, const int32_t *hidders, int accumulate) {
+    EH_ENTER(c);
+    auto *v = c->sviews;
+    if (!v) { set_error("surface_ray_cross: the view store is not enabled (edgehip_surface_views_enable)"); return EDGEHIP_ERR_STATE; }
+    const bool every = !targets && !hidders && n_pairs < 0;
+    if (!every && (n_pairs < 0 || (n_pairs > 0 && (!targets || !hidders)))) {
+        set_error("surface_ray_cross: n_pairs >= 0 needs both lists; both NULL with n_pairs < 0 means every ordered pair");
+        return EDGEHIP_ERR_ARG;
+    }
+    const int cap = v->p.capacity;
+    std::vector<int2> list;
+    if (every) {
+        for (int t = 0; t < cap; t++)
+            for (int h = 0; h < cap; h++)
+                if (t != h && v->stored.has(t) && v->stored.has(h)) list.push_back(make_int2(t, h));
+    } else {
+        for (int j = 0; j < n_pairs; j++) {
+            const int t = targets[j], h = hidders[j];
+            if (t < 0 || t >= cap || h < 0 || h >= cap) { set_error("surface_ray_cross: view out of range"); return EDGEHIP_ERR_ARG; }
+            if (t == h) { set_error("surface_ray_cross: a pair needs two different views"); return EDGEHIP_ERR_ARG; }
+        }
+        for (int j = 0; j < n_pairs; j++)   // checkDFRayCrossExaustive returns at once when either key frame has no grid (:73)
+            if (v->stored.has(targets[j]) && v->stored.has(hidders[j])) list.push_back(make_int2(targets[j], hidders[j]));
+    }
+    const size_t G = (size_t)v->gw * v->gh;
+    if (!accumulate) EH_CHECK(hipMemsetAsync(v->vis, 1, (size_t)cap * G, c->stream));   // ResetVisibility
+    if (list.empty()) return 0;
+    if (list.size() > v->pairs_cap) {
+        if (v->pairs) EH_CHECK(hipFree(v->pairs));   // waits for the launches that read it
+        v->pairs = nullptr;
+        v->pairs_cap = 0;
+        if (hipMalloc((void **)&v->pairs, list.size() * sizeof(int2)) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("surface_ray_cross: device allocation of the pair list failed");
+            return EDGEHIP_ERR_MEMORY;
+        }
+        v->pairs_cap = list.size();
+    }
+    EH_CHECK(hipMemcpyAsync(v->pairs, list.data(), list.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));   // pageable: staged on return
+    hipLaunchKernelGGL(k_sv_ray_cross, dim3((unsigned)list.size(), (unsigned)((G + kSvThreads - 1) / kSvThreads)), dim3(kSvThreads), 0, c->stream,
+                       sv_store(c), sv_geom(c), (const int2 *)v->pairs);
     EH_LAUNCH_CHECK();
     return 0;
 }

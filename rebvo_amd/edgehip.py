@@ -229,7 +229,7 @@ EXPORTS = [
     "edgehip_download_depth_image", "edgehip_download_depth_images_batch", "edgehip_depth_image_device",
     "edgehip_surface_views_enable", "edgehip_surface_view_capture", "edgehip_surface_view_upload", "edgehip_surface_view_clear",
     "edgehip_surface_space", "edgehip_surface_integrate", "edgehip_download_surface_visibility",
-    "edgehip_download_surface_visibilities_batch",
+    "edgehip_download_surface_visibilities_batch", "edgehip_surface_ray_cross",
 ]
 
 _lib = None
@@ -807,6 +807,18 @@ class EdgeHip:
                 cast = np.zeros(1, np.int32)   # an empty list is not NULL ("every stored view")
             ptr = cast.ctypes.data_as(C.c_void_p)
         self._ck(self.lib.edgehip_surface_integrate(self.ctx, _dp(origin), _dp(size), n, ptr, int(bool(accumulate))))
+
+    def surface_ray_cross(self, pairs=None, accumulate=False):
+        """edgehip_surface_ray_cross: checkDFRayCrossExaustive for the ordered pairs [(target, hidder), ...] (None: every ordered pair of
+        stored views), in-stream; the flags come back through download_surface_visibility."""
+        if pairs is None:
+            n, pt, ph = -1, None, None
+        else:
+            pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+            n = len(pr)
+            t, h = (np.ascontiguousarray(pr[:, k]) if n else np.zeros(1, np.int32) for k in (0, 1))
+            pt, ph = t.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p)
+        self._ck(self.lib.edgehip_surface_ray_cross(self.ctx, n, pt, ph, int(bool(accumulate))))
 
     def download_surface_visibility(self, views):
         """edgehip_download_surface_visibility(_batch): one slot -> (gh, gw) bool array; a sequence of slots -> a list of them."""
