@@ -275,8 +275,8 @@ __device__ __forceinline__ bool tile_trange(const MatchRec &r, int tx0, int ty0,
     // t-range whose samples can round into the tile [tx0,tx0+FT) x [ty0,ty0+FT): pixel x = round(u t + c) is inside iff
     // u t + c lies in [tx0 - 0.5, tx0 + FT - 0.5]; conservative by 0.01 px (the sample is evaluated in float: < 1e-4 px off)
     // and by a slack on t that covers the rounding of the bounds (c and the reciprocal: relative 1e-7, amplified by 1/u).
-    // Every sample kept here is still tested against the tile exactly; a sample dropped here must be outside.  Both users —
-    // the binning and the rasteriser — go through this one function.  (v_rcp_f32 + products instead of IEEE divisions.)
+    // A sample dropped here must be outside; the rasteriser trims what is kept to the exact run with the per-sample test at its two
+    // ends (k_field_raster).  Both users — the binning and, for a radius beyond the packed bin entry, the rasteriser — go through this one function.  (v_rcp_f32 + products instead of IEEE divisions.)
     float tlo = (float)(-radius), thi = (float)(radius - 1);
     const float bx0 = (float)tx0 - 0.51f - r.c_px, bx1 = (float)(tx0 + FT) - 0.49f - r.c_px;
     const float by0 = (float)ty0 - 0.51f - r.c_py, by1 = (float)(ty0 + FT) - 0.49f - r.c_py;
@@ -297,12 +297,25 @@ __device__ __forceinline__ bool tile_trange(const MatchRec &r, int tx0, int ty0,
     return t0 <= t1;
 }
 
+// A bin entry is 4 bytes.  PACKED (radius <= kPackedRadiusMax, the host's choice per launch): the KeyLine id in the low half and
+// the tile's conservative t-range next to it, t0 + radius in byte 2 and t1 + radius in byte 3 (0 .. 2 radius - 1 <= 253), so
+// that tile_trange is evaluated once per (KeyLine, tile) — here — and the rasteriser reads its result.  Otherwise the entry
+// is the bare id and the rasteriser calls tile_trange itself.
+constexpr int kPackedRadiusMax = 127;
+constexpr int kRngSlots = 9;   // tiles of a bounding box whose ranges pass A parks in LDS for pass B (3 x 3: the shipped search ranges)
+
+__device__ __forceinline__ uint32_t pack_trange(int t0, int t1, int radius) {
+    return (uint32_t)(t0 + radius) | ((uint32_t)(t1 + radius) << 8);
+}
+
+template <bool PACKED>
 __global__ __launch_bounds__(256) void k_field_bin(const KlSoA *kls, const int32_t *__restrict__ kns,
                                                    const float *__restrict__ retuned, int32_t *__restrict__ bin_cnt,
                                                    int32_t *__restrict__ bins, int w, int h, int radius, float min_mod_arg,
                                                    int ntx, int nty, int bin_cap, unsigned long long *__restrict__ fwd_key,
                                                    int32_t *__restrict__ fwd_win) {
     __shared__ int s_cnt[kMaxTiles], s_base[kMaxTiles];
+    __shared__ uint16_t s_rng[PACKED ? kRngSlots * 256 : 1];   // [slot][thread]: a thread's own ranges, 0xFFFF = the tile is not touched
     const int seq = blockIdx.z, tid = threadIdx.x;
     const int i = blockIdx.x * 256 + tid;
     const int kn = kns[seq];
@@ -332,15 +345,20 @@ __global__ __launch_bounds__(256) void k_field_bin(const KlSoA *kls, const int32
     }
     // pass A: count per tile (LDS).  Which tiles of the bounding box the segment really touches is remembered in a bit mask
     // for pass B (up to 32 tiles: always at the shipped search ranges, where a segment spans at most 3 x 3)
+    // (PACKED: pass B needs the range itself, so pass A parks it in LDS — up to kRngSlots tiles, else pass B evaluates it again:
+    // the same function on the same operands, the same entries)
     const int bw = txb - txa + 1;
-    const bool cached = bw > 0 && (tyb - tya + 1) * bw <= 32;
+    const bool cached = bw > 0 && (tyb - tya + 1) * bw <= (PACKED ? kRngSlots : 32);
     uint32_t hitmask = 0;
     for (int ty = tya; ty <= tyb; ty++)
         for (int tx = txa; tx <= txb; tx++) {
             int t0, t1;
-            if (tile_trange(r, tx * FT, ty * FT, radius, t0, t1)) {
-                atomicAdd(&s_cnt[ty * ntx + tx], 1);
-                if (cached) hitmask |= 1u << ((ty - tya) * bw + (tx - txa));
+            const bool hit = tile_trange(r, tx * FT, ty * FT, radius, t0, t1);
+            if (hit) atomicAdd(&s_cnt[ty * ntx + tx], 1);
+            if constexpr (PACKED) {
+                if (cached) s_rng[((ty - tya) * bw + (tx - txa)) * 256 + tid] = hit ? (uint16_t)pack_trange(t0, t1, radius) : (uint16_t)0xFFFFu;
+            } else {
+                if (hit && cached) hitmask |= 1u << ((ty - tya) * bw + (tx - txa));
             }
         }
     __syncthreads();
@@ -354,10 +372,20 @@ __global__ __launch_bounds__(256) void k_field_bin(const KlSoA *kls, const int32
     for (int ty = tya; ty <= tyb; ty++)
         for (int tx = txa; tx <= txb; tx++) {
             int t0, t1;
-            if (cached ? ((hitmask >> ((ty - tya) * bw + (tx - txa))) & 1u) != 0u : tile_trange(r, tx * FT, ty * FT, radius, t0, t1)) {
+            bool hit;
+            uint32_t entry = (uint32_t)i;
+            if constexpr (PACKED) {
+                uint32_t rng;
+                if (cached) { rng = s_rng[((ty - tya) * bw + (tx - txa)) * 256 + tid]; hit = rng != 0xFFFFu; }
+                else { hit = tile_trange(r, tx * FT, ty * FT, radius, t0, t1); rng = hit ? pack_trange(t0, t1, radius) : 0u; }
+                entry |= rng << 16;
+            } else {
+                hit = cached ? ((hitmask >> ((ty - tya) * bw + (tx - txa))) & 1u) != 0u : tile_trange(r, tx * FT, ty * FT, radius, t0, t1);
+            }
+            if (hit) {
                 const int t = ty * ntx + tx;
                 const int pos = s_base[t] + atomicAdd(&s_cnt[t], 1);
-                if (pos < bin_cap) bins[((size_t)seq * ntiles + t) * bin_cap + pos] = i;
+                if (pos < bin_cap) bins[((size_t)seq * ntiles + t) * bin_cap + pos] = (int32_t)entry;
             }
         }
     // whole-frame driver: this kernel visits every KeyLine of the NEW edge map right before the minimisation, so it also
@@ -369,6 +397,7 @@ __global__ __launch_bounds__(256) void k_field_bin(const KlSoA *kls, const int32
 #ifndef EDGEHIP_NT_RASTER
 #define EDGEHIP_NT_RASTER 1   // the 16-bit plane as streaming stores: B.build_field 1162 -> 1154 us, the evaluations that gather from it unchanged
 #endif
+template <bool PACKED>
 __global__ __launch_bounds__(256) void k_field_raster(const KlSoA *kls, int32_t *__restrict__ bin_cnt,
                                                       const int32_t *__restrict__ bins, uint32_t *__restrict__ field,
                                                       uint16_t *__restrict__ field16, size_t f16stride, int f16tx, int keep32,
@@ -403,34 +432,31 @@ __global__ __launch_bounds__(256) void k_field_raster(const KlSoA *kls, int32_t 
 #endif
 #ifndef EDGEHIP_RASTER_ABL
 #define EDGEHIP_RASTER_ABL 0   // timing experiments only, wrong fields by design (tools/experiments/CALLS.md: r04_r): 1 plain store for
-#endif                         // the atomic, 2 no LDS access, 3 no samples, 4 = 3 and no output stage, 5 = 3 and no record gather, 6 = 5 and no bin read
+#endif                         // the atomic, 2 no LDS access, 3 no samples (bin read, gather, range and trim only), 4 = 3 and no output stage, 5 = 3 and no record gather
 #ifndef EDGEHIP_RASTER_UNROLL
-#define EDGEHIP_RASTER_UNROLL 2   // 1198 -> 1156 us per 1024 frames (same-box A/B, tools/experiments/CALLS.md: r04_g)
+#define EDGEHIP_RASTER_UNROLL 2   // samples per trip of the test-free loop
 #endif
     // (A split chosen per tile so that the last round of 256 threads is as full as possible — 1..4 parts, block-uniform —
     // measured slower, 1198 -> 1283 us: the run-time divisor costs every item more than the fuller rounds save.  So did dealing the
     // samples of 256 KeyLines to the threads in equal shares (ranges parked in LDS, a scan of their lengths, one binary search per
     // thread, then a flat walk over samples and KeyLines): 1158 -> 1434 us — the ablations say why: the sample loop already runs at
     // ~17 lane-cycles per sample for ~16 vector instructions, i.e. with nearly full lanes; the flat walk adds instructions to every
-    // sample and saves waiting that is not there.  Where the kernel's ~970 us go (r = 40, 15.4 k KeyLines, profiles/r04_r_raster_ablations.txt):
-    // samples 526, the 16-bit plane's store 160 (0.74 GB: the HBM rate), record gathers 104, bin reads 57, tile clear / ranges / ramp ~120.)
+    // sample and saves waiting that is not there.  Where the kernel's ~970 us went before the test-free loop (r = 40, 15.4 k KeyLines,
+    // profiles/r04_r_raster_ablations.txt): samples 526, the 16-bit plane's store 160 (0.74 GB: the HBM rate), record gathers 104, bin
+    // reads 57, tile clear / ranges / ramp ~120.)
     constexpr int FSPLIT = EDGEHIP_FSPLIT;
     // The hardware rounding differs from round() in a way that matters only for a coordinate of exactly -0.5 (pixel 0
     // instead of -1, ctx.h): that can only be accepted by a tile that starts at column / row 0, so only the tiles on
     // the left / top image border pay for the fix-up.  (Block-uniform choice of one of four loop bodies.)
-#ifndef EDGEHIP_RASTER_LEAN
-#define EDGEHIP_RASTER_LEAN 1
-#endif
     const unsigned ex4 = ex << 2;
     const int neg4tx0 = -4 * tx0;
-    auto raster = [&](auto fix_x, auto fix_y, auto narrow) {
+    const unsigned org = (unsigned)(neg4tx0 - ty0 * (TS * 4));   // byte offset of pixel (0, 0) of the image relative to the tile's first word
+    const float radius_f = (float)radius;
+    auto raster = [&](auto fix_x, auto fix_y) {
         for (int wi = tid; wi < cnt * FSPLIT; wi += 256) {
             const int li = wi / FSPLIT, part = wi - li * FSPLIT;
-#if EDGEHIP_RASTER_ABL == 6     // no bin read
-            const int ikl = li * 7;
-#else
-            const int ikl = list[li];
-#endif
+            const uint32_t entry = (uint32_t)list[li];
+            const int ikl = PACKED ? (int)(entry & 0xFFFFu) : (int)entry;
 #if EDGEHIP_RASTER_ABL >= 5     // no record gather
             MatchRec r;
             r.c_px = (float)(tx0 + (ikl & 63)); r.c_py = (float)(ty0 + ((ikl >> 6) & 63)); r.u_mx = 0.6f; r.u_my = 0.8f;
@@ -439,8 +465,73 @@ __global__ __launch_bounds__(256) void k_field_raster(const KlSoA *kls, int32_t 
             MatchRec r;
             { const float4 q = ldg(reinterpret_cast<const float4 *>(k.rec), 2 * (size_t)ikl); r.c_px = q.x; r.c_py = q.y; r.u_mx = q.z; r.u_my = q.w; }
 #endif
-            int t0, t1;
-            if (!tile_trange(r, tx0, ty0, radius, t0, t1)) continue;
+            // The conservative range: from the bin entry (bytes 2 and 3, each one conversion), or evaluated here.  t runs as a float
+            // (|t| <= 255: every value and the increment are exact), so the reference's (float)t costs nothing and |t| is an operand
+            // modifier of the one conversion back.
+            float lo, hi;
+            if constexpr (PACKED) {
+                lo = (float)((entry >> 16) & 0xFFu) - radius_f;
+                hi = (float)(entry >> 24) - radius_f;
+            } else {
+                int t0, t1;
+                if (!tile_trange(r, tx0, ty0, radius, t0, t1)) continue;
+                lo = (float)t0; hi = (float)t1;
+            }
+#ifndef EDGEHIP_RASTER_PK
+#define EDGEHIP_RASTER_PK 0   // 1: x and y of a sample as one packed pair (v_pk_mul_f32 + v_pk_add_f32, each component rounded like the scalar op): two
+                              // instructions fewer per sample on paper, 6 % SLOWER measured (B.build_field 1155 -> 1230 us per 1024 frames, same box,
+                              // profiles/r06_raster_pad_and_packed_ab.txt): the packed forms issue at half rate and want their operands in register pairs
+#endif
+#if EDGEHIP_RASTER_PK
+            typedef float v2f __attribute__((ext_vector_type(2)));
+            const v2f u2 = {r.u_mx, r.u_my}, c2 = {r.c_px, r.c_py};
+#endif
+            // A sample's float position: global_tracker.cpp:78.  Image::GetIndexRC rounds it with round().
+            auto at = [&](const float tf, float &fx, float &fy) __attribute__((always_inline)) {
+#if EDGEHIP_RASTER_PK
+                const v2f t2 = {tf, tf};
+                const v2f f2 = u2 * t2 + c2;             // the same two float expressions (no contraction: -ffp-contract=off)
+                fx = f2.x; fy = f2.y;
+#else
+                fx = r.u_mx * tf + r.c_px;               // same float expression
+                fy = r.u_my * tf + r.c_py;
+#endif
+            };
+            // in the tile AND in the image (ex, ey): the exact test, the one every sample used to pay.  The column as a byte offset,
+            // (round(fx) << 2) - 4 tx0 against 4 ex, in one shift-add (|lx| is far below 2^29).
+            auto inside = [&](const float tf) __attribute__((always_inline)) -> bool {
+                float fx, fy;
+                at(tf, fx, fy);
+                const int rx = decltype(fix_x)::value ? round_half_away_i(fx) : round_ties_up_i(fx);
+                const int ry = decltype(fix_y)::value ? round_half_away_i(fy) : round_ties_up_i(fy);
+                return (unsigned)((rx << 2) + neg4tx0) < ex4 && (unsigned)(ry - ty0) < ey;
+            };
+            // Why only the ENDS of the range are tested.  t is an exact small integer in a float.  For a fixed KeyLine, fl(u * t) is
+            // monotone in t (a correctly rounded product of a constant: non-decreasing for u >= 0, non-increasing for u < 0, also where
+            // it is flushed to zero), fl(. + c) is monotone in its operand, and so is either rounding to a pixel (round-half-away and the
+            // hardware's ties-up conversion are both non-decreasing).  So the column is a monotone function of t and "tx0 <= column <
+            // tx0 + ex" holds on one contiguous run of t; likewise the row; the image clip is part of the same two intervals (ex, ey
+            // < FT on the right / bottom tiles).  The intersection of two runs is one run.  tile_trange's range contains every
+            // in-tile sample (it only ever drops samples that are outside), so walking inwards from both ends to the first sample that
+            // passes the exact test yields exactly that run, and every sample between the two is in the tile: the loop below stores
+            // without a test.  The slack of the conservative range is a fraction of a sample for all but nearly axis-parallel segments
+            // (0.01 px / |u| + 0.25), so the walk is one or two tests per end.
+            if constexpr (FSPLIT == 2) {
+                // the two threads of a KeyLine are neighbouring lanes (wi = 2 li + part; cnt * 2 is even, so both are in the loop
+                // together, and both took the same branch above): one walks up from lo, the other down from hi, in ONE loop for the
+                // wave, and they swap what they found
+                const float step = part ? -1.f : 1.f;
+                float tf = part ? hi : lo;
+                for (float n = hi - lo; n >= 0.f && !inside(tf); n -= 1.f) tf += step;   // stops one beyond the far end if nothing is inside
+                const float other = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(tf), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]: lane ^ 1
+                lo = part ? other : tf;
+                hi = part ? tf : other;
+            } else {
+                while (lo <= hi && !inside(lo)) lo += 1.f;
+                while (hi > lo && !inside(hi)) hi -= 1.f;
+            }
+            if (lo > hi) continue;   // nothing of this KeyLine rounds into the tile
+            int t0 = (int)lo, t1 = (int)hi;
             {
                 const int chunk = (t1 - t0 + FSPLIT) / FSPLIT;   // ceil(len / FSPLIT)
                 t0 += part * chunk;
@@ -454,62 +545,37 @@ __global__ __launch_bounds__(256) void k_field_raster(const KlSoA *kls, int32_t 
             if (t0 == 12345) s_tile[0] = idk;
             continue;
 #endif
-            // t runs as a float (|t| <= 255: every value and the increment are exact), so the reference's (float)t costs
-            // nothing and |t| is an operand modifier of the one conversion back
-            const float t1f = (float)t1;
-#ifndef EDGEHIP_RASTER_PK
-#define EDGEHIP_RASTER_PK 0   // 1: x and y of a sample as one packed pair (v_pk_mul_f32 + v_pk_add_f32, each component rounded like the scalar op): two
-                              // instructions fewer per sample on paper, 6 % SLOWER measured (B.build_field 1155 -> 1230 us per 1024 frames, same box,
-                              // profiles/r06_raster_pad_and_packed_ab.txt): the packed forms issue at half rate and want their operands in register pairs
-#endif
-#if EDGEHIP_RASTER_PK
-            typedef float v2f __attribute__((ext_vector_type(2)));
-            const v2f u2 = {r.u_mx, r.u_my}, c2 = {r.c_px, r.c_py};
-#endif
+            // |t|, an exact small integer in a float, goes into byte 2 of the stored word with v_cvt_pk_u8_f32 (one instruction for the
+            // conversion, the shift and the OR; |t| <= radius <= 255: build_field_enqueue refuses a larger radius)
+            // A sample of the run is inside under round(), so its coordinates are not -0.5 and the bare conversion gives round()'s pixel in
+            // every tile: the border tiles' fix-up is paid by the end tests only.  Its row is >= ty0 >= 0, so the tile's origin folds into
+            // one block-uniform constant: row * (4 TS) + org as one 24-bit multiply-add (the 32-bit product runs at a quarter of the rate),
+            // the column's shift-add on top.
             auto sample = [&](const float tf) __attribute__((always_inline)) {
-#if EDGEHIP_RASTER_PK
-                const v2f t2 = {tf, tf};
-                const v2f f2 = u2 * t2 + c2;             // global_tracker.cpp:78, the same two float expressions (no contraction: -ffp-contract=off)
-                const float fx = f2.x, fy = f2.y;
-#else
-                const float fx = r.u_mx * tf + r.c_px;   // global_tracker.cpp:78, same float expression
-                const float fy = r.u_my * tf + r.c_py;
-#endif
-                // Image::GetIndexRC uses round()
-#if EDGEHIP_RASTER_LEAN && EDGEHIP_RASTER_ABL == 0
-                // Two vector instructions fewer per in-tile sample (of ~16; the loop runs the vector ALU at 1.0): the column comes out as a BYTE offset
-                // in one shift-add — (round(fx) << 2) - 4 tx0, compared against 4 ex: the same test, |lx| is far below 2^29 — and |t|, an exact small
-                // integer in a float, goes into byte 2 of the stored word with v_cvt_pk_u8_f32 (one instruction for the conversion, the shift and the OR;
-                // |t| <= radius <= 255 is the host's condition for this form: `narrow`).
-                const int rx = decltype(fix_x)::value ? round_half_away_i(fx) : round_ties_up_i(fx);
-                const int ly = (decltype(fix_y)::value ? round_half_away_i(fy) : round_ties_up_i(fy)) - ty0;
-                const unsigned lx4 = (unsigned)((rx << 2) + neg4tx0);
-                if (lx4 >= ex4 || (unsigned)ly >= ey) return;
-                const uint32_t val = decltype(narrow)::value ? __builtin_amdgcn_cvt_pk_u8_f32(fabsf(tf), 2u, idk) : (((uint32_t)fabsf(tf) << 16) | idk);
-                atomicMin(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(s_tile) + (__umul24((unsigned)ly, (unsigned)(TS * 4)) + lx4)), val);
-#else
-                const int lx = (decltype(fix_x)::value ? round_half_away_i(fx) : round_ties_up_i(fx)) - tx0;
-                const int ly = (decltype(fix_y)::value ? round_half_away_i(fy) : round_ties_up_i(fy)) - ty0;
-                if ((unsigned)lx >= ex || (unsigned)ly >= ey) return;
-                const uint32_t at = (uint32_t)fabsf(tf);
+                float fx, fy;
+                at(tf, fx, fy);
+                const unsigned off = ((unsigned)round_ties_up_i(fx) << 2) + (__umul24((unsigned)round_ties_up_i(fy), (unsigned)(TS * 4)) + org);
+                const uint32_t val = __builtin_amdgcn_cvt_pk_u8_f32(fabsf(tf), 2u, idk);
+                uint32_t *const px = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(s_tile) + off);
 #if EDGEHIP_RASTER_ABL == 1      // a plain store instead of the atomic
-                s_tile[ly * TS + lx] = (at << 16) | idk;
+                *px = val;
 #elif EDGEHIP_RASTER_ABL == 2    // no LDS access at all
-                acc_abl += (at << 16) | idk | (uint32_t)(ly * TS + lx);
+                acc_abl += val | off;
 #else
-                atomicMin(&s_tile[__umul24((unsigned)ly, (unsigned)TS) + (unsigned)lx], (at << 16) | idk);   // (a 24-bit product: the 32-bit one runs at a quarter of the rate, once per sample)
-#endif
+                atomicMin(px, val);
 #endif
             };
-#if EDGEHIP_RASTER_UNROLL == 2
-            // two samples per trip: the loop's own bookkeeping (exec-mask save / restore, compare, branch: as many scalar
-            // instructions as the sample's arithmetic) is paid once per pair
+            // straight-line: no bounds test, no early-out, so no exec-mask save / restore inside a trip
+            constexpr int UNROLL = EDGEHIP_RASTER_UNROLL;
+            const float t1f = (float)t1;
             float tf = (float)t0;
-            for (; tf + 1.f <= t1f; tf += 2.f) { sample(tf); sample(tf + 1.f); }
-            if (tf <= t1f) sample(tf);
-#else
-            for (float tf = (float)t0; tf <= t1f; tf += 1.f) sample(tf);
-#endif
+            if constexpr (UNROLL > 1) {
+                for (; tf + (float)(UNROLL - 1) <= t1f; tf += (float)UNROLL) {
+#pragma unroll
+                    for (int j = 0; j < UNROLL; j++) sample(tf + (float)j);
+                }
+            }
+            for (; tf <= t1f; tf += 1.f) sample(tf);
 #if EDGEHIP_RASTER_ABL == 2
             if (acc_abl == 0x12345u) s_tile[1] = acc_abl;
 #endif
@@ -517,13 +583,8 @@ __global__ __launch_bounds__(256) void k_field_raster(const KlSoA *kls, int32_t 
     };
     using T = std::true_type;
     using F = std::false_type;
-    if (radius <= 255) {
-        if (tx0 == 0) { if (ty0 == 0) raster(T{}, T{}, T{}); else raster(T{}, F{}, T{}); }
-        else { if (ty0 == 0) raster(F{}, T{}, T{}); else raster(F{}, F{}, T{}); }
-    } else {
-        if (tx0 == 0) { if (ty0 == 0) raster(T{}, T{}, F{}); else raster(T{}, F{}, F{}); }
-        else { if (ty0 == 0) raster(F{}, T{}, F{}); else raster(F{}, F{}, F{}); }
-    }
+    if (tx0 == 0) { if (ty0 == 0) raster(T{}, T{}); else raster(T{}, F{}); }
+    else { if (ty0 == 0) raster(F{}, T{}); else raster(F{}, F{}); }
     __syncthreads();
     if (tid == 0) bin_cnt[(size_t)seq * kMaxTiles + tile] = 0;   // every tile's count is consumed by exactly this block: ready for the next k_field_bin (no memset launch)
 #if EDGEHIP_RASTER_ABL == 4
@@ -3129,11 +3190,19 @@ int build_field_enqueue(edgehip_ctx *c, int slot, int radius, float min_mod, boo
     c->field_radius = radius;
     const int ntx = (pl.w + FT - 1) / FT, nty = (pl.h + FT - 1) / FT;
     if (c->field_mode == 0 && ntx * nty <= kMaxTiles) {
-        hipLaunchKernelGGL(k_field_bin, dim3((pl.cap + 255) / 256, 1, pl.nseq), dim3(256), 0, c->stream, kldev(c, slot),
+        // The bin entry carries the tile's t-range beside a 16-bit KeyLine id where both fit (every shipped configuration: search_range 40);
+        // otherwise it is the bare id and the rasteriser evaluates the range itself.  Both kernels of a launch take the same form.
+#ifndef EDGEHIP_FIELD_PACKED_RANGE
+#define EDGEHIP_FIELD_PACKED_RANGE 1
+#endif
+        const bool packed = EDGEHIP_FIELD_PACKED_RANGE && radius <= kPackedRadiusMax && pl.cap <= 65536;
+        auto bin = packed ? k_field_bin<true> : k_field_bin<false>;
+        auto raster = packed ? k_field_raster<true> : k_field_raster<false>;
+        hipLaunchKernelGGL(bin, dim3((pl.cap + 255) / 256, 1, pl.nseq), dim3(256), 0, c->stream, kldev(c, slot),
                            c->kn_slot + (size_t)slot * pl.nseq, c->retuned_slot + (size_t)slot * pl.nseq, c->bin_cnt, c->bins,
                            pl.w, pl.h, radius, min_mod, ntx, nty, pl.cap, clear_fwd ? c->fwd_key : nullptr, clear_fwd ? c->fwd_win : nullptr);
         c->fwd_cleared = clear_fwd;
-        hipLaunchKernelGGL(k_field_raster, dim3(ntx, nty, pl.nseq), dim3(256), 0, c->stream, kldev(c, slot), c->bin_cnt,
+        hipLaunchKernelGGL(raster, dim3(ntx, nty, pl.nseq), dim3(256), 0, c->stream, kldev(c, slot), c->bin_cnt,
                            c->bins, c->field, c->field16, pl.f16stride, pl.f16tx, c->p.debug_planes ? 1 : 0, pl.w, pl.h,
                            pl.fstride, pl.ftx, radius, ntx, pl.cap);
         c->field32_valid = c->p.debug_planes != 0;
