@@ -455,10 +455,12 @@ int edgehip_build_undistort_map(const edgehip_params *params, int32_t *inx, int3
 int edgehip_download_undistorted(edgehip_ctx *ctx, int seq, int slot, uint8_t *rgb24);
 
 /* ---- dense depth fill (the visualizer's depth_filler) ----------------------------------------------------------------
- * The inverse-depth grid that depth_filler interpolates from a KeyLine list (src/visualizer/depth_filler.cpp), in the order both of
- * the reference's callers run it — ResetData, FillEdgeData(edge_tracker&, ThreshRelRho, ThreshMatchNum, discart), InitCoarseFine,
- * Integrate(IterNum) — the visualizer per received frame (src/visualizer/visualizer.cpp:303, 436-440) and the key-frame path per key
- * frame (src/mtracklib/keyframe.cpp:171-184, app/kf_visualizer/main.cpp:106).  Grid gw x gh = (w / block_w) x (h / block_h), cell
+ * The inverse-depth grid that depth_filler interpolates from a KeyLine list (src/visualizer/depth_filler.cpp), in the order the
+ * reference's callers run it — ResetData, FillEdgeData, InitCoarseFine, Integrate(IterNum).  FillEdgeData has two overloads with
+ * different gates.  The key-frame path fills from the tracker's list per key frame, FillEdgeData(edge_tracker&, ThreshRelRho,
+ * ThreshMatchNum, discart) (src/mtracklib/keyframe.cpp:171-184, app/kf_visualizer/main.cpp:106): that is edgehip_depth_fill.  The
+ * visualizer fills per received frame from the quantised wire records, FillEdgeData(net_keyline*, kn, p_off, ...)
+ * (src/visualizer/visualizer.cpp:303, 436-440): that is edgehip_depth_fill_net, below.  Grid gw x gh = (w / block_w) x (h / block_h), cell
  * (x, y) at y * gw + x.  rho, s_rho and fixed equal the reference's bit for bit (fp64 throughout, the reference's order of
  * operations; tests/depth_fill_port.py restates it) — except the sign and payload of a NaN the arithmetic creates (inf - inf,
  * 0 * inf): the GPU's default NaN is positive, x86 SSE's negative.  NaNs a KeyLine carries in pass through unchanged.  Two departures, both where the reference has no defined result or writes
@@ -497,6 +499,77 @@ int edgehip_download_depth_grid(edgehip_ctx *ctx, int seq, double *rho, double *
  * array or entry may be NULL.  Synchronises once. */
 int edgehip_download_depth_grids_batch(edgehip_ctx *ctx, int n, const int32_t *seqs, double *const *rho, double *const *s_rho,
                                        uint8_t *const *fixed);
+
+/* ---- the wire-format edge map (net_keyline) and the visualizer's fill from it ---------------------------------------------
+ * The reference publishes every frame's edge map as 15-byte net_keyline records (include/CommLib/net_keypoint.h:35-62), packed by
+ * copy_net_keyline + copy_net_keyline_nextid (src/CommLib/net_keypoint.cpp:29-108) in its third thread
+ * (src/rebvo/rebvo_third_t.cpp:189-203); its visualizer builds the dense depth from those records (visualizer.cpp:427-440).  Here the
+ * records are packed on the device from the SoA KeyLines, for every sequence in one launch: 15 B per KeyLine leave the device instead
+ * of the 168-byte record. */
+#pragma pack(push, 1)
+typedef struct edgehip_net_keyline {   /* rebvo::net_keyline, byte for byte */
+    uint16_t qx, qy;        /* round(c_p) */
+    uint16_t rho, s_rho;    /* max(clamp_ushort(NET_RHO_SCALING * v / k_prof), 1), NET_RHO_SCALING = 10000 */
+    int32_t n_kl;           /* record index of the next KeyLine on the edge, -1: none */
+    uint8_t m_num;          /* clamp_uchar(m_num) */
+    uint8_t flow_x, flow_y; /* extra.flow: matched displacement * 10 + 127, or the stereo disparity + 127 (the `gradient` arm is never written upstream) */
+} edgehip_net_keyline;
+#pragma pack(pop)
+#ifdef __cplusplus
+static_assert(sizeof(edgehip_net_keyline) == 15, "net_keyline is 15 bytes on the wire");
+#else
+_Static_assert(sizeof(edgehip_net_keyline) == 15, "net_keyline is 15 bytes on the wire");
+#endif
+/* The three fields of net_packet_hdr (net_keypoint.h:64-78) that describe the records (rebvo_third_t.cpp:192, 200, 202). */
+typedef struct edgehip_net_header {
+    int32_t kline_num;      /* records packed: min(kn, kl_size) */
+    int32_t km_num;         /* NumMatches(): directed_matching's count of the frame processed last (edgehip_seq_state::klm_num when the
+                               records were packed; the device keeps no count per slot) */
+    float k;                /* the k_prof the records were scaled with, as float (net_hdr->k = pbuf.K) */
+} edgehip_net_header;
+/* Allocates the record store: nseq x kl_size records back to back (nseq * kl_size * 15 B, rounded up to 16) and nseq headers, all
+ * zero.  kl_size is the reference's KEYLINE_MAX argument (rebvo_third_t.cpp:193, 197); it need not equal max_points.  kl_size == 0
+ * frees the store.  EDGEHIP_ERR_ARG for kl_size < 0 or > EDGEHIP_KEYLINE_MAX; EDGEHIP_ERR_MEMORY when the allocation fails (the store
+ * is then off; the context stays usable). */
+int edgehip_net_enable(edgehip_ctx *ctx, int kl_size);
+/* copy_net_keyline(*ef, pair, to, kl_size, k_prof) followed by copy_net_keyline_nextid(*ef, to, kl_size)
+ * (net_keypoint.cpp:29-75, 79-108; rebvo_third_t.cpp:192-202) on the KeyLines of `slot`, for every sequence, in-stream (no
+ * synchronisation).  KeyLine j is packed iff j < min(kn, kl_size), into record j.  slot_pair >= 0: the slot of the stereo pair's edge
+ * map (needs params.stereo_available); extra.flow is then the disparity to KeyLine stereo_m_id of that slot (:45-58).  k_prof: host
+ * array [nseq] of the scale each sequence's depths are divided by, or NULL for each sequence's edgehip_seq_state::K.  Fields are formed
+ * by the reference's own operations (float / double as written there, clamp_ushort and clamp_uchar taking a float), so the records
+ * equal the reference's byte for byte.  Departures, where the reference has no defined result:
+ *   - n_kl of a KeyLine whose n_id was not packed in this call (n_id >= kline_num) is -1; the reference copies that KeyLine's
+ *     net_id, which is stale from an earlier call.
+ *   - a stereo_m_id past the KeyLine capacity counts as no match (flow 127, 127); the reference indexes the pair list with it.
+ *   - converting a NaN (or a value past the integer range) to an integer has no defined result in C++; the kernel's conversions
+ *     behave as an x86-64 build of the reference does for finite values and are otherwise unspecified.
+ * Only the first kline_num * 15 bytes of a sequence's records are written.  EDGEHIP_ERR_STATE when the store is off, or with a pair
+ * slot on a context without the stereo fields; EDGEHIP_ERR_ARG for a slot out of range or slot_pair == slot. */
+int edgehip_net_pack(edgehip_ctx *ctx, int slot, int slot_pair /* -1: none */, const double *k_prof /* [nseq] or NULL */);
+/* The records of sequence `seq` and their header: records has room for kl_size entries, of which header->kline_num are copied.
+ * Either may be NULL.  Synchronises. */
+int edgehip_download_net_keylines(edgehip_ctx *ctx, int seq, edgehip_net_keyline *records, edgehip_net_header *header);
+/* The same for n sequences seqs[n] (records[j], headers[j] per request; any array or entry may be NULL).  Synchronises once. */
+int edgehip_download_net_keylines_batch(edgehip_ctx *ctx, int n, const int32_t *seqs, edgehip_net_keyline *const *records,
+                                        edgehip_net_header *const *headers);
+/* The stores of sequences [first, first+count) into DEVICE memory of the context's GPU, records_dev[count][kl_size] records (15 B each,
+ * back to back) and headers_dev[count] (either may be NULL; e.g. torch uint8 tensors), without a host bounce — like
+ * edgehip_depth_image_device.  The copy is complete on return. */
+int edgehip_net_keylines_device(edgehip_ctx *ctx, int first, int count, void *records_dev, void *headers_dev);
+/* The receiving side (visualizer.cpp:427-428): kn records that came from elsewhere become sequence `seq`'s stored records, header
+ * {kn, 0, 1}.  0 <= kn <= kl_size; the bytes behind them are left alone.  The array is free on return. */
+int edgehip_upload_net_keylines(edgehip_ctx *ctx, int seq, const edgehip_net_keyline *records, int32_t kn);
+/* d_filler[0].ResetData(); FillEdgeData(net_kl, net_kln, p_off, DF_ThreshRelRho, DF_ThreshMatchNum); InitCoarseFine();
+ * Integrate(DF_IterNum) (visualizer.cpp:436-439; depth_filler.cpp:41-56, 59-104, 233-355) on every sequence's stored records,
+ * in-stream, with the parameters of edgehip_depth_fill_enable (discard included; the visualizer's call leaves it at true).  Per
+ * record: rho and s_rho divided by NET_RHO_SCALING; skipped when s_rho / rho > thresh_rel_rho; m_num < thresh_match_num skips it
+ * (discard) or sets s_rho = RHO_MAX; cell GetIndex((qx + p_off_x) / block_w, (qy + p_off_y) / block_h) in float, converted as
+ * edgehip_depth_fill converts (an index past the grid is dropped).  No p_id / n_id / rho <= 0 gate and no rho0: that is the other
+ * overload.  Writes the same grids as edgehip_depth_fill — edgehip_depth_surface, the grid downloads and
+ * edgehip_surface_view_capture work on the result unchanged — and shares no other state with it.  EDGEHIP_ERR_STATE when either the
+ * fill or the record store is off. */
+int edgehip_depth_fill_net(edgehip_ctx *ctx, float p_off_x, float p_off_y);
 
 /* ---- depth surface (what depth_filler's callers take from the grid) --------------------------------------------------------
  * From the grids of the last edgehip_depth_fill, for every sequence, in the camera frame and bit for bit as depth_filler computes them

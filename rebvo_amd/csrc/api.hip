@@ -647,6 +647,7 @@ int edgehip_destroy(edgehip_ctx *c) {
     (void)hipStreamSynchronize(c->stream_a);
     (void)hipStreamSynchronize(c->stream);
     depth_fill_free(c);
+    net_free(c);
     CtxAllocs *mine = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_allocs_mu);

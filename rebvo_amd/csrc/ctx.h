@@ -584,6 +584,9 @@ struct edgehip_ctx {
     // edgehip_surface_views_enable: stored views (grid + pose) and the voxel plane of the cross-view surface integration (surface_integrate.hip); null when off
     struct SurfaceViews;
     SurfaceViews *sviews = nullptr;
+    // edgehip_net_enable: every sequence's edge map as 15-byte wire records (net_keyline) and their headers (net_keyline.hip); null when off
+    struct NetStore;
+    NetStore *net = nullptr;
 };
 
 namespace edgehip {
@@ -701,6 +704,9 @@ void depth_fill_free(edgehip_ctx *c);               // depth_fill.hip: edgehip_d
 int depth_fill_geometry(edgehip_ctx *c, int32_t *gw, int32_t *gh, int32_t *bw, int32_t *bh);   // depth_fill.hip: EDGEHIP_ERR_STATE when off
 bool depth_fill_grids(edgehip_ctx *c, const double **rho, const double **s_rho);   // depth_fill.hip: false before the first fill
 void depth_surface_free(edgehip_ctx *c);            // depth_surface.hip
+void net_free(edgehip_ctx *c);                      // net_keyline.hip: edgehip_net_enable(ctx, 0), edgehip_destroy
+// net_keyline.hip: the record store ([nseq][kl_size] records of 15 B, back to back) and its headers; false when off
+bool net_store(edgehip_ctx *c, const uint8_t **records, const edgehip_net_header **headers, int *kl_size);
 void surface_views_free(edgehip_ctx *c);            // surface_integrate.hip
 
 }  // namespace edgehip

@@ -13,6 +13,11 @@
 //                t-3 .. t-1, the four below / to the right by sweep k-1 at steps t-3 .. t-1 and by sweep k not before t+1: exactly the
 //                values the raster loop reads, in one buffer.  (With a skew of 3 sweep k+1 would reach (x-1, y-1) at the step at which
 //                sweep k updates (x, y).)  No two cells of one step are neighbours.
+// Two sources feed stages 1 and 2 (template parameter NET of k_depth_fill; stages 3 and 4 are the same code for both):
+//   NET = false  the slot's SoA KeyLines with FillEdgeData(edge_tracker&, ...)'s gates (:113-163): the key-frame path's overload;
+//   NET = true   a sequence's 15-byte wire records (net_keyline.hip) with FillEdgeData(net_keyline*, kn, p_off, ...)'s (:59-104): the
+//                visualizer's overload (visualizer.cpp:436-439).  rho and s_rho come back from their 1 / NET_RHO_SCALING quanta, the cell from
+//                (qx + p_off.x) / bl_size.w in float; there is no p_id / n_id / rho <= 0 gate and no rho0.
 // The grid lives in LDS while it fits in 64 KB (rho, s_rho: 16 B per cell, fixed: 1 B — 3 600 cells at 10-px blocks of 752x480)
 // and in the context's output arrays in HBM otherwise (14 400 cells at 5-px blocks); the code is the same on both.
 // fp64 throughout; '/' and sqrt are the compiler's correctly rounded operations, the cell index uses its correctly rounded float
@@ -48,7 +53,26 @@ struct DfArgs {
     int cap, gw, gh, bw, bh, iter_num, bound_mode, discard, m_num_t, ntiles;
     double v_thresh;
     int use_lds;
+    // NET: the wire records instead of kls / kns
+    const uint8_t *net_rec;              // [nseq][net_kl_size][15]
+    const edgehip_net_header *net_hdr;   // [nseq]
+    int net_kl_size;
+    float p_off_x, p_off_y;
 };
+
+constexpr double kNetRhoScale = 10000.0;   // NET_RHO_SCALING, include/CommLib/net_keypoint.h:32
+// the fields FillEdgeData reads of wire record i (net_keyline: qx, qy, rho, s_rho at bytes 0 .. 7, m_num at byte 12), byte loads: a record is aligned to nothing
+struct DfNetRec { int qx, qy, rho, s_rho, m_num; };
+__device__ __forceinline__ DfNetRec df_net_rec(const uint8_t *rec, int i) {
+    const uint8_t *p = rec + (size_t)i * 15;
+    DfNetRec r;
+    r.qx = ldg(p, 0) | (ldg(p, 1) << 8);
+    r.qy = ldg(p, 2) | (ldg(p, 3) << 8);
+    r.rho = ldg(p, 4) | (ldg(p, 5) << 8);
+    r.s_rho = ldg(p, 6) | (ldg(p, 7) << 8);
+    r.m_num = ldg(p, 12);
+    return r;
+}
 
 // (uint) of a float as an x86-64 build converts it (cvttss2si to 64 bits, low 32 bits): what GetIndex receives (image.h:113)
 __device__ __forceinline__ uint32_t x86_f2u(float q) {
@@ -62,13 +86,15 @@ __device__ __forceinline__ bool df_inboundary(int x, int y, int gw, int gh, int 
     return false;
 }
 
+template <bool NET>
 __global__ __launch_bounds__(kDfThreads) void k_depth_fill(DfArgs a, DfLevels lv) {
     extern __shared__ __align__(16) unsigned char df_lds[];
     __shared__ int32_t part[kDfThreads];
     const int seq = blockIdx.x, tid = threadIdx.x;
     const int gw = a.gw, gh = a.gh, G = gw * gh;
-    const KlSoA &k = a.kls[seq];
-    const int kn = min(a.kns[seq], a.cap);
+    const KlSoA &k = a.kls[NET ? 0 : seq];   // (NET: not read)
+    const int kn = NET ? max(0, min(min(a.net_hdr[seq].kline_num, a.net_kl_size), a.cap)) : min(a.kns[seq], a.cap);
+    const uint8_t *nrec = NET ? a.net_rec + (size_t)seq * a.net_kl_size * 15 : nullptr;
     int32_t *cell = a.cell + (size_t)seq * a.cap;
     int32_t *cnt = a.cnt + (size_t)seq * G;
     int32_t *off = a.off + (size_t)seq * (G + 1);
@@ -85,8 +111,20 @@ __global__ __launch_bounds__(kDfThreads) void k_depth_fill(DfArgs a, DfLevels lv
 
     // 1. cells (FillEdgeData's tests, in its order) and counts
     for (int i = tid; i < kn; i += kDfThreads) {
-        const double r = ldg(k.rho, i), s = ldg(k.s_rho, i);
         int c = -1;
+        if constexpr (NET) {
+            const DfNetRec n = df_net_rec(nrec, i);
+            const double r = n.rho / kNetRhoScale, s = n.s_rho / kNetRhoScale;
+            if (!(s / r > a.v_thresh) && !(n.m_num < a.m_num_t && a.discard)) {
+                // (nkl.qx + p_off.x) / bl_size.w: u_short -> int -> float, float sum, float quotient by the u_int block size
+                const uint32_t idx = x86_f2u(((float)n.qy + a.p_off_y) / (float)a.bh) * (uint32_t)gw + x86_f2u(((float)n.qx + a.p_off_x) / (float)a.bw);
+                if (idx < (uint32_t)G) c = (int)idx;   // past the last cell: dropped, as below
+            }
+            cell[i] = c;
+            if (c >= 0) atomicAdd(&cnt[c], 1);
+            continue;
+        }
+        const double r = ldg(k.rho, i), s = ldg(k.s_rho, i);
         if (!(s / r > a.v_thresh)) {
             const bool weak = ldg(k.m_num, i) < a.m_num_t || ldg(k.p_id, i) < 0 || ldg(k.n_id, i) < 0 || r <= 0;
             if (!(weak && a.discard)) {
@@ -148,12 +186,21 @@ __global__ __launch_bounds__(kDfThreads) void k_depth_fill(DfArgs a, DfLevels lv
         double cr = 1.0, cs = kRhoMax * 2, I = 1.0 / ((kRhoMax * 2) * (kRhoMax * 2));
         for (int j = b0; j < b1; j++) {
             const int i = ids[j];
-            double r = ldg(k.rho, i);
-            const double s = ldg(k.s_rho, i);
-            double kl_I = 1.0 / (s * s);
-            if (ldg(k.m_num, i) < a.m_num_t || ldg(k.p_id, i) < 0 || ldg(k.n_id, i) < 0 || r <= 0) {
-                kl_I = 1.0 / (kRhoMax * kRhoMax);
-                if (r < 0) r = ldg(k.rho0, i);   // (the reference writes this back into the KeyLine; the device only reads)
+            double r, kl_I;
+            if constexpr (NET) {
+                const DfNetRec n = df_net_rec(nrec, i);
+                r = n.rho / kNetRhoScale;
+                double s = n.s_rho / kNetRhoScale;
+                if (n.m_num < a.m_num_t) s = kRhoMax;   // (discard: such a record got no cell)
+                kl_I = 1 / (s * s);
+            } else {
+                r = ldg(k.rho, i);
+                const double s = ldg(k.s_rho, i);
+                kl_I = 1.0 / (s * s);
+                if (ldg(k.m_num, i) < a.m_num_t || ldg(k.p_id, i) < 0 || ldg(k.n_id, i) < 0 || r <= 0) {
+                    kl_I = 1.0 / (kRhoMax * kRhoMax);
+                    if (r < 0) r = ldg(k.rho0, i);   // (the reference writes this back into the KeyLine; the device only reads)
+                }
             }
             double i_rho = I * cr;
             i_rho += r * kl_I;
@@ -269,13 +316,17 @@ struct edgehip_ctx::DepthFill {
     int32_t *cell, *cnt, *off, *ids, *tile_n;
     double *tile_r, *tile_s, *rho, *s_rho;
     uint8_t *fixed;
-    bool filled = false;   // an edgehip_depth_fill was enqueued since the enable
+    bool filled = false;   // an edgehip_depth_fill / edgehip_depth_fill_net was enqueued since the enable
+    // edgehip_depth_fill_net with more records per sequence than the KeyLine capacity: cell / ids of its own (grown, never shrunk)
+    int32_t *net_scratch = nullptr;
+    int net_scratch_cap = 0;
 };
 
 static void depth_fill_release(edgehip_ctx *c) {
     if (!c->dfill) return;
     (void)hipStreamSynchronize(c->stream);
     if (c->dfill->arena) (void)hipFree(c->dfill->arena);
+    if (c->dfill->net_scratch) (void)hipFree(c->dfill->net_scratch);
     delete c->dfill;
     c->dfill = nullptr;
 }
@@ -391,13 +442,50 @@ int edgehip_depth_fill(edgehip_ctx *c, int slot) {
     a.iter_num = d->p.iter_num; a.bound_mode = d->p.bound_mode; a.discard = d->p.discard != 0; a.m_num_t = d->p.thresh_match_num;
     a.ntiles = d->ntiles; a.v_thresh = d->p.thresh_rel_rho; a.use_lds = d->use_lds;
     const size_t lds = d->use_lds ? (size_t)d->gw * d->gh * 17 : 0;
-    hipLaunchKernelGGL(k_depth_fill, dim3(c->plan.nseq), dim3(kDfThreads), lds, c->stream, a, d->lv);
+    a.net_rec = nullptr; a.net_hdr = nullptr; a.net_kl_size = 0; a.p_off_x = a.p_off_y = 0.f;
+    hipLaunchKernelGGL(k_depth_fill<false>, dim3(c->plan.nseq), dim3(kDfThreads), lds, c->stream, a, d->lv);
     EH_LAUNCH_CHECK();
     d->filled = true;
     if (c->stream_a != c->stream) {   // a later stage A that detects into this slot waits for the fill's reads
         EH_CHECK(hipEventRecord(c->ev_use[slot], c->stream));
         c->use_valid[slot] = true;
     }
+    return 0;
+}
+
+int edgehip_depth_fill_net(edgehip_ctx *c, float p_off_x, float p_off_y) {
+    EH_ENTER(c);
+    auto *d = c->dfill;
+    if (!d) { set_error("depth_fill_net: depth fill is not enabled (edgehip_depth_fill_enable)"); return EDGEHIP_ERR_STATE; }
+    DfArgs a;
+    if (!net_store(c, &a.net_rec, &a.net_hdr, &a.net_kl_size)) { set_error("depth_fill_net: the record store is not enabled (edgehip_net_enable)"); return EDGEHIP_ERR_STATE; }
+    a.cell = d->cell; a.ids = d->ids; a.cap = c->plan.cap;
+    if (a.net_kl_size > c->plan.cap) {   // more records than KeyLines fit: binning scratch of that size
+        const size_t B = c->plan.nseq;
+        if (d->net_scratch_cap < a.net_kl_size) {
+            EH_CHECK(hipStreamSynchronize(c->stream));
+            if (d->net_scratch) { (void)hipFree(d->net_scratch); d->net_scratch = nullptr; d->net_scratch_cap = 0; }
+            void *q = nullptr;
+            if (hipMalloc(&q, 4 * 2 * B * (size_t)a.net_kl_size) != hipSuccess) { (void)hipGetLastError(); set_error("depth_fill_net: device allocation failed"); return EDGEHIP_ERR_MEMORY; }
+            d->net_scratch = (int32_t *)q;
+            d->net_scratch_cap = a.net_kl_size;
+        }
+        a.cap = d->net_scratch_cap;
+        a.cell = d->net_scratch;
+        a.ids = d->net_scratch + B * (size_t)a.cap;
+    }
+    a.kls = kldev(c, 0); a.kns = c->kn_slot;   // not read
+    a.cnt = d->cnt; a.off = d->off;
+    a.tile_r = d->tile_r; a.tile_s = d->tile_s; a.tile_n = d->tile_n;
+    a.rho = d->rho; a.s_rho = d->s_rho; a.fixed = d->fixed;
+    a.gw = d->gw; a.gh = d->gh; a.bw = d->p.block_w; a.bh = d->p.block_h;
+    a.iter_num = d->p.iter_num; a.bound_mode = d->p.bound_mode; a.discard = d->p.discard != 0; a.m_num_t = d->p.thresh_match_num;
+    a.ntiles = d->ntiles; a.v_thresh = d->p.thresh_rel_rho; a.use_lds = d->use_lds;
+    a.p_off_x = p_off_x; a.p_off_y = p_off_y;
+    const size_t lds = d->use_lds ? (size_t)d->gw * d->gh * 17 : 0;
+    hipLaunchKernelGGL(k_depth_fill<true>, dim3(c->plan.nseq), dim3(kDfThreads), lds, c->stream, a, d->lv);
+    EH_LAUNCH_CHECK();
+    d->filled = true;
     return 0;
 }
 

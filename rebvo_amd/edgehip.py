@@ -26,6 +26,13 @@ KEYLINE_DTYPE = np.dtype(
 )
 assert KEYLINE_DTYPE.itemsize == 168
 
+# edgehip_net_keyline = rebvo::net_keyline (include/CommLib/net_keypoint.h:35-62), packed: 15 bytes
+NET_KEYLINE_DTYPE = np.dtype({"names": ["qx", "qy", "rho", "s_rho", "n_kl", "m_num", "flow"],
+                              "formats": ["<u2", "<u2", "<u2", "<u2", "<i4", "u1", ("u1", (2,))],
+                              "offsets": [0, 2, 4, 6, 8, 12, 13], "itemsize": 15})
+assert NET_KEYLINE_DTYPE.itemsize == 15
+NET_HEADER_DTYPE = np.dtype([("kline_num", "<i4"), ("km_num", "<i4"), ("k", "<f4")])   # edgehip_net_header
+
 
 class Params(C.Structure):
     _fields_ = [
@@ -230,6 +237,8 @@ EXPORTS = [
     "edgehip_surface_views_enable", "edgehip_surface_view_capture", "edgehip_surface_view_upload", "edgehip_surface_view_clear",
     "edgehip_surface_space", "edgehip_surface_integrate", "edgehip_download_surface_visibility",
     "edgehip_download_surface_visibilities_batch", "edgehip_surface_ray_cross",
+    "edgehip_net_enable", "edgehip_net_pack", "edgehip_download_net_keylines", "edgehip_download_net_keylines_batch",
+    "edgehip_net_keylines_device", "edgehip_upload_net_keylines", "edgehip_depth_fill_net",
 ]
 
 _lib = None
@@ -692,6 +701,63 @@ class EdgeHip:
         pf = (C.c_void_p * n)(*[o[2].ctypes.data for o in out])
         self._ck(self.lib.edgehip_download_depth_grids_batch(self.ctx, n, seqs.ctypes.data_as(C.c_void_p), pr, ps, pf))
         return [(r, s, f.astype(bool)) for r, s, f in out]
+
+    # ---- the wire-format edge map (net_keyline) and the visualizer's fill from it ----
+    def net_enable(self, kl_size):
+        """edgehip_net_enable: room for kl_size 15-byte records per sequence; 0 (or None) frees the store."""
+        self._ck(self.lib.edgehip_net_enable(self.ctx, int(kl_size or 0)))
+        self.net_kl_size = int(kl_size or 0)
+
+    def net_pack(self, slot, slot_pair=-1, k_prof=None):
+        """edgehip_net_pack: copy_net_keyline + copy_net_keyline_nextid on the KeyLines of `slot` for every sequence (in-stream).
+        k_prof: one scale per sequence (or a scalar), None for each sequence's K."""
+        kp = None
+        if k_prof is not None:
+            kp = np.ascontiguousarray(np.broadcast_to(np.asarray(k_prof, np.float64), (self.nseq,))).copy()
+        self._ck(self.lib.edgehip_net_pack(self.ctx, int(slot), int(slot_pair), _dp(kp) if kp is not None else None))
+
+    def net_keylines(self, seq):
+        """edgehip_download_net_keylines -> (records, header): a NET_KEYLINE_DTYPE array of header["kline_num"] records and a
+        NET_HEADER_DTYPE scalar."""
+        rec = np.zeros(self.net_kl_size, NET_KEYLINE_DTYPE)
+        hdr = np.zeros(1, NET_HEADER_DTYPE)
+        self._ck(self.lib.edgehip_download_net_keylines(self.ctx, int(seq), C.c_void_p(rec.ctypes.data), C.c_void_p(hdr.ctypes.data)))
+        return rec[:max(0, min(int(hdr["kline_num"][0]), self.net_kl_size))].copy(), hdr[0]
+
+    def net_keylines_batch(self, seqs):
+        """edgehip_download_net_keylines_batch -> [(records, header)] in the order of seqs (one synchronisation)."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.int32)
+        n = len(seqs)
+        recs = [np.zeros(self.net_kl_size, NET_KEYLINE_DTYPE) for _ in range(n)]
+        hdrs = [np.zeros(1, NET_HEADER_DTYPE) for _ in range(n)]
+        pr = (C.c_void_p * n)(*[r.ctypes.data for r in recs])
+        ph = (C.c_void_p * n)(*[h.ctypes.data for h in hdrs])
+        self._ck(self.lib.edgehip_download_net_keylines_batch(self.ctx, n, seqs.ctypes.data_as(C.c_void_p), pr, ph))
+        return [(r[:max(0, min(int(h["kline_num"][0]), self.net_kl_size))].copy(), h[0]) for r, h in zip(recs, hdrs)]
+
+    def net_keylines_into(self, records=None, headers=None, first=0):
+        """edgehip_net_keylines_device: the whole stores of sequences [first, first + count) into uint8 torch tensors on the context's
+        device, records (count, kl_size, 15) and headers (count, 12) (either may be None), device to device."""
+        t = records if records is not None else headers
+        count = t.shape[0]
+        for x, tail in ((records, (self.net_kl_size, 15)), (headers, (NET_HEADER_DTYPE.itemsize,))):
+            if x is not None:
+                assert x.dtype.itemsize == 1 and x.is_contiguous(), "uint8 contiguous tensors"
+                assert tuple(x.shape) == (count,) + tail, (tuple(x.shape), (count,) + tail)
+        self._ck(self.lib.edgehip_net_keylines_device(self.ctx, int(first), int(count),
+                                                      C.c_void_p(records.data_ptr() if records is not None else None),
+                                                      C.c_void_p(headers.data_ptr() if headers is not None else None)))
+
+    def upload_net_keylines(self, seq, records):
+        """edgehip_upload_net_keylines: `records` (NET_KEYLINE_DTYPE, or raw uint8 of shape (kn, 15)) become sequence seq's stored records."""
+        rec = np.ascontiguousarray(records)
+        if rec.dtype != NET_KEYLINE_DTYPE:
+            rec = np.ascontiguousarray(rec, np.uint8).reshape(-1, 15)
+        self._ck(self.lib.edgehip_upload_net_keylines(self.ctx, int(seq), C.c_void_p(rec.ctypes.data), len(rec)))
+
+    def depth_fill_net(self, p_off=(0.0, 0.0)):
+        """edgehip_depth_fill_net: the grids of every sequence from its stored wire records (in-stream)."""
+        self._ck(self.lib.edgehip_depth_fill_net(self.ctx, C.c_float(p_off[0]), C.c_float(p_off[1])))
 
     # ---- depth surface (computeDistance / calcSurfNormals / calcSurfArea / getImgRho*) ----
     def depth_surface_enable(self, surface=True, image_mode=0):
