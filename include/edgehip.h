@@ -699,6 +699,81 @@ int edgehip_download_surface_visibility(edgehip_ctx *ctx, int view, uint8_t *vis
 /* The same for n slots views[n] (vis[j] per request; an entry may be NULL).  Synchronises once. */
 int edgehip_download_surface_visibilities_batch(edgehip_ctx *ctx, int n, const int32_t *views, uint8_t *const *vis);
 
+/* ---- the ROS nodelet's per-frame output: point cloud and EdgeMap records ---------------------------------------------------
+ * The one output callback that ships with the reference is the ROS nodelet's, RebvoNodelet::edgeMapPubCb
+ * (ros/src/rebvo_ros/src/rebvo_nodelet.cpp:146-217).  Per KeyLine its loop (:176-212) builds one xyz float point of the rebvo_pcl cloud,
+ * cam.unprojectHomCordVec(makeVector(kl.p_m.x, kl.p_m.y, kl.rho / K)) (:203-208; include/UtilLib/cam_model.h:163-169), and one Keyline
+ * record of the EdgeMap message (:179-198; ros/src/rebvo_ros/msg/Keyline.msg).  Here both are packed on the device from the SoA
+ * KeyLines, for every sequence in one launch: 12 B and / or 52 B per KeyLine leave the device instead of the 168-byte record.
+ *   point:   q = rho / K; x = (float)(p_m.x / q / zfm), y = (float)(p_m.y / q / zfm), z = (float)(1.0 / q) — fp64 quotients in the
+ *            reference's order, each correctly rounded, zfm the slot camera's (edgehip_set_slot_camera's rule), the narrowing to float
+ *            round-to-nearest-even with float denormals kept.  Bit for bit the reference's, except the sign and payload of a NaN the
+ *            divisions create (0 / 0, inf / inf: the GPU's default NaN is positive, x86 SSE's negative); a NaN rho passes through as a NaN.
+ *   record:  the fields below; rho is NOT divided by K, as in the nodelet.  The two int16 fields keep the low 16 bits of p_id / n_id,
+ *            what the nodelet's assignment does on x86-64.
+ * edgehip_ros_keyline is the little-endian ROS wire body of one element of `Keyline[] Keylines` (fixed-size fields in message order,
+ * no padding), so n records are the serialised array's body element for element; edgehip_ros_point is one point of a PointCloud2 with
+ * the fields "xyz" (point_step 12). */
+typedef struct edgehip_ros_point { float x, y, z; } edgehip_ros_point;
+#pragma pack(push, 1)
+typedef struct edgehip_ros_keyline {   /* rebvo/Keyline.msg, field for field */
+    float KlGrad[2];        /* m_m */
+    float KlImgPos[2];      /* c_p */
+    double invDepth;        /* rho */
+    double invDepthS;       /* s_rho */
+    float KlFocPos[2];      /* p_m */
+    int32_t KlMatchID;      /* m_id */
+    int32_t ConsMatch;      /* m_num */
+    int16_t KlPrevMatchID;  /* (int16_t)p_id */
+    int16_t KlNextMatchID;  /* (int16_t)n_id */
+} edgehip_ros_keyline;
+#pragma pack(pop)
+#ifdef __cplusplus
+static_assert(sizeof(edgehip_ros_point) == 12, "a PointCloud2 xyz point is 12 bytes");
+static_assert(sizeof(edgehip_ros_keyline) == 52, "a Keyline.msg record is 52 bytes on the wire");
+#else
+_Static_assert(sizeof(edgehip_ros_point) == 12, "a PointCloud2 xyz point is 12 bytes");
+_Static_assert(sizeof(edgehip_ros_keyline) == 52, "a Keyline.msg record is 52 bytes on the wire");
+#endif
+#define EDGEHIP_ROS_POINTS 1
+#define EDGEHIP_ROS_KEYLINES 2
+/* Allocates the chosen stores, zeroed: nseq x max_points records of each kind, back to back (a sequence's records start at
+ * seq * max_points * 12 resp. * 52 bytes), and nseq counts.  what == 0 frees them.  EDGEHIP_ERR_ARG for other bits than the two above;
+ * EDGEHIP_ERR_MEMORY when the allocation fails (the stores are then off; the context stays usable). */
+int edgehip_ros_enable(edgehip_ctx *ctx, int what);
+/* The loop of rebvo_nodelet.cpp:176-212 on the KeyLines of `slot`, for every sequence, in-stream (no synchronisation): KeyLine j goes
+ * to record j of each enabled store, j < kn, and kn to the sequence's count.  Reads exactly what edgehip_download_keylines returns for
+ * the slot — for the OLD slot of a processed frame, its turned p_m / m_m / rho / s_rho (see there).  k_prof: host array [nseq] of the K
+ * each sequence's rho is divided by (edgeMapRebvo.K, :204), or NULL for each sequence's edgehip_seq_state::K.  Only the kn records of a
+ * sequence are written.  EDGEHIP_ERR_STATE when the stores are off, EDGEHIP_ERR_ARG for a slot out of range. */
+int edgehip_ros_pack(edgehip_ctx *ctx, int slot, const double *k_prof /* [nseq] or NULL */);
+/* The records of sequence `seq` from the last edgehip_ros_pack: points / keylines have room for max_points entries, of which *kn_out are
+ * copied.  Any destination may be NULL (as is one whose store is not enabled).  Synchronises. */
+int edgehip_download_ros_edgemap(edgehip_ctx *ctx, int seq, edgehip_ros_point *points, edgehip_ros_keyline *keylines, int32_t *kn_out);
+/* The same for n sequences seqs[n] (points[j], keylines[j], kn_out[j] per request; any array or entry may be NULL).  Synchronises once. */
+int edgehip_download_ros_edgemaps_batch(edgehip_ctx *ctx, int n, const int32_t *seqs, edgehip_ros_point *const *points,
+                                        edgehip_ros_keyline *const *keylines, int32_t *kn_out);
+/* The whole stores of sequences [first, first+count) into DEVICE memory of the context's GPU: points_dev[count][max_points] (12 B each),
+ * keylines_dev[count][max_points] (52 B each, back to back), kn_dev[count] int32 (any may be NULL; a store that is not enabled is
+ * EDGEHIP_ERR_STATE), without a host bounce — like edgehip_net_keylines_device.  The copy is complete on return. */
+int edgehip_ros_edgemap_device(edgehip_ctx *ctx, int first, int count, void *points_dev, void *keylines_dev, void *kn_dev);
+/* TEST SUPPORT ONLY, not part of the product surface: the other direction, same shapes and rules (no counts) — device memory becomes the
+ * stores' bytes of sequences [first, first+count), so that a test can put a sentinel behind the records and see that a pack leaves it
+ * alone.  The next edgehip_ros_pack overwrites what it covers; nothing in the library reads the stores back. */
+int edgehip_ros_edgemap_from_device(edgehip_ctx *ctx, int first, int count, const void *points_dev, const void *keylines_dev);
+/* The same products for output callbacks at full pipeline depth, with the semantics of edgehip_export_keylines / _fetch / _wait (above)
+ * and a staging ring of their own: the OLD slot of the frame processed last, packed in-stream for sequences seqs[n] with k_prof[n] (required:
+ * the callback of frame k-1 divides by pbuf.K of frame k-1, which the device no longer holds), what = EDGEHIP_ROS_POINTS |
+ * EDGEHIP_ROS_KEYLINES (needs no edgehip_ros_enable); at most four tickets outstanding.  The staging grows with n and with the record kinds asked
+ * for, which it can only do while no ticket is outstanding (EDGEHIP_ERR_STATE otherwise: ask for the largest request first).  Fetch enqueues the copies of exactly kn[j] records
+ * into points_dst[j] / keylines_dst[j] (either array or any entry may be NULL; page-locked destinations are written by DMA) on a copy
+ * stream.  Wait blocks until they have landed and releases the ticket; for a ticket that was never fetched it waits for the pack itself, so
+ * that the staging entry is not reused under a kernel that has yet to write it. */
+int edgehip_ros_export(edgehip_ctx *ctx, int n, const int32_t *seqs, const double *k_prof, int what, int *ticket_out);
+int edgehip_ros_export_fetch(edgehip_ctx *ctx, int ticket, const int32_t *kn, edgehip_ros_point *const *points_dst,
+                             edgehip_ros_keyline *const *keylines_dst);
+int edgehip_ros_export_wait(edgehip_ctx *ctx, int ticket);
+
 /* ---- measurement ------------------------------------------------------------------------------------- */
 /* Names of the kernel groups timed by the built-in HIP-event profiler, and their accumulated device time.
  * edgehip_profile_enable(ctx, 1) brackets every launch group with events on the context stream (adds host

@@ -648,6 +648,7 @@ int edgehip_destroy(edgehip_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     depth_fill_free(c);
     net_free(c);
+    ros_free(c);
     CtxAllocs *mine = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_allocs_mu);
@@ -1619,3 +1620,5 @@ int edgehip_profile_read(edgehip_ctx *c, double *ms, int64_t *calls) {
 }
 
 }  // extern "C"
+
+bool edgehip::host_range_registered(const void *p, size_t bytes) { return host_registered(p, bytes); }

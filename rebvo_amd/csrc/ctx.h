@@ -587,6 +587,9 @@ struct edgehip_ctx {
     // edgehip_net_enable: every sequence's edge map as 15-byte wire records (net_keyline) and their headers (net_keyline.hip); null when off
     struct NetStore;
     NetStore *net = nullptr;
+    // edgehip_ros_enable / edgehip_ros_export: the ROS nodelet's point cloud and EdgeMap records (ros_edgemap.hip); null when never used
+    struct RosStore;
+    RosStore *ros = nullptr;
 };
 
 namespace edgehip {
@@ -708,5 +711,7 @@ void net_free(edgehip_ctx *c);                      // net_keyline.hip: edgehip_
 // net_keyline.hip: the record store ([nseq][kl_size] records of 15 B, back to back) and its headers; false when off
 bool net_store(edgehip_ctx *c, const uint8_t **records, const edgehip_net_header **headers, int *kl_size);
 void surface_views_free(edgehip_ctx *c);            // surface_integrate.hip
+void ros_free(edgehip_ctx *c);                      // ros_edgemap.hip: the stores and the export ring, edgehip_destroy
+bool host_range_registered(const void *p, size_t bytes);  // api.hip: [p, p + bytes) lies inside a range page-locked by edgehip_register_host
 
 }  // namespace edgehip

@@ -32,6 +32,15 @@ NET_KEYLINE_DTYPE = np.dtype({"names": ["qx", "qy", "rho", "s_rho", "n_kl", "m_n
                               "offsets": [0, 2, 4, 6, 8, 12, 13], "itemsize": 15})
 assert NET_KEYLINE_DTYPE.itemsize == 15
 NET_HEADER_DTYPE = np.dtype([("kline_num", "<i4"), ("km_num", "<i4"), ("k", "<f4")])   # edgehip_net_header
+# edgehip_ros_point / edgehip_ros_keyline: what the ROS nodelet builds per KeyLine (ros/src/rebvo_ros/src/rebvo_nodelet.cpp:176-212):
+# one xyz point of the cloud, one rebvo/Keyline.msg record (its little-endian wire body, packed: 52 bytes)
+ROS_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
+ROS_KEYLINE_DTYPE = np.dtype({"names": ["KlGrad", "KlImgPos", "invDepth", "invDepthS", "KlFocPos", "KlMatchID", "ConsMatch",
+                                        "KlPrevMatchID", "KlNextMatchID"],
+                              "formats": [("<f4", 2), ("<f4", 2), "<f8", "<f8", ("<f4", 2), "<i4", "<i4", "<i2", "<i2"],
+                              "offsets": [0, 8, 16, 24, 32, 40, 44, 48, 50], "itemsize": 52})
+assert ROS_POINT_DTYPE.itemsize == 12 and ROS_KEYLINE_DTYPE.itemsize == 52
+ROS_POINTS, ROS_KEYLINES = 1, 2   # EDGEHIP_ROS_POINTS, EDGEHIP_ROS_KEYLINES
 
 
 class Params(C.Structure):
@@ -239,6 +248,8 @@ EXPORTS = [
     "edgehip_download_surface_visibilities_batch", "edgehip_surface_ray_cross",
     "edgehip_net_enable", "edgehip_net_pack", "edgehip_download_net_keylines", "edgehip_download_net_keylines_batch",
     "edgehip_net_keylines_device", "edgehip_upload_net_keylines", "edgehip_depth_fill_net",
+    "edgehip_ros_enable", "edgehip_ros_pack", "edgehip_download_ros_edgemap", "edgehip_download_ros_edgemaps_batch",
+    "edgehip_ros_edgemap_device", "edgehip_ros_edgemap_from_device", "edgehip_ros_export", "edgehip_ros_export_fetch", "edgehip_ros_export_wait",
 ]
 
 _lib = None
@@ -285,6 +296,7 @@ class EdgeHip:
         self.lib = load_library()
         self.p, self.nseq, self.nslots = params, nseq, nslots
         self.w, self.h, self.cap = params.w, params.h, min(params.max_points, 50000)
+        self.ros_what = 0   # the stores edgehip_ros_enable has switched on through this wrapper
         self.ctx = C.c_void_p()
         self._ck(self.lib.edgehip_create(C.byref(params), nseq, nslots, device, C.byref(self.ctx)))
 
@@ -760,6 +772,99 @@ class EdgeHip:
         self._ck(self.lib.edgehip_depth_fill_net(self.ctx, C.c_float(p_off[0]), C.c_float(p_off[1])))
 
     # ---- depth surface (computeDistance / calcSurfNormals / calcSurfArea / getImgRho*) ----
+    # ---- the ROS nodelet's output: point cloud and EdgeMap records ----
+    def ros_enable(self, what):
+        """edgehip_ros_enable: the stores of `what` (ROS_POINTS | ROS_KEYLINES), cap records per sequence each; 0 (or None) frees them."""
+        self._ck(self.lib.edgehip_ros_enable(self.ctx, int(what or 0)))
+        self.ros_what = int(what or 0)
+
+    def ros_pack(self, slot, k_prof=None):
+        """edgehip_ros_pack: the nodelet's loop on the KeyLines of `slot` for every sequence (in-stream).  k_prof: [nseq] scales, or
+        None = each sequence's seq_state.K."""
+        kp = None if k_prof is None else np.ascontiguousarray(k_prof, dtype=np.float64)
+        assert kp is None or kp.shape == (self.nseq,)
+        self._ck(self.lib.edgehip_ros_pack(self.ctx, int(slot), _dp(kp) if kp is not None else None))
+
+    def ros_edgemap(self, seq):
+        """edgehip_download_ros_edgemap -> (points, keylines, kn): ROS_POINT_DTYPE / ROS_KEYLINE_DTYPE arrays of kn records (None for a
+        store that is not enabled)."""
+        return self.ros_edgemaps_batch([seq])[0]
+
+    def ros_edgemaps_batch(self, seqs):
+        """edgehip_download_ros_edgemaps_batch -> [(points, keylines, kn)] in the order of seqs."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.int32)
+        n = len(seqs)
+        what = self.ros_what
+        if not what:
+            raise EdgeHipError("ros_edgemaps_batch: no store is enabled (ros_enable)")
+        pts = [np.zeros(self.cap, ROS_POINT_DTYPE) if what & ROS_POINTS else None for _ in range(n)]
+        kls = [np.zeros(self.cap, ROS_KEYLINE_DTYPE) if what & ROS_KEYLINES else None for _ in range(n)]
+        pp = (C.c_void_p * n)(*[None if b is None else b.ctypes.data for b in pts])
+        pk = (C.c_void_p * n)(*[None if b is None else b.ctypes.data for b in kls])
+        kn = np.zeros(n, np.int32)
+        self._ck(self.lib.edgehip_download_ros_edgemaps_batch(self.ctx, n, seqs.ctypes.data_as(C.c_void_p), pp, pk, kn.ctypes.data_as(C.c_void_p)))
+        return [(None if p is None else p[:k].copy(), None if q is None else q[:k].copy(), int(k)) for p, q, k in zip(pts, kls, kn)]
+
+    def ros_edgemap_into(self, points=None, keylines=None, kn=None, first=0):
+        """edgehip_ros_edgemap_device: the whole stores of sequences [first, first + count) into torch tensors on the context's device —
+        points uint8 (count, cap, 12), keylines uint8 (count, cap, 52), kn int32 (count,); any may be None."""
+        given = [x for x in (points, keylines, kn) if x is not None]
+        count = given[0].shape[0]
+        for x, tail, item in ((points, (self.cap, 12), 1), (keylines, (self.cap, 52), 1), (kn, (), 4)):
+            if x is not None:
+                assert x.is_cuda and x.is_contiguous() and x.element_size() == item and tuple(x.shape) == (count,) + tail, tuple(x.shape)
+        self._ck(self.lib.edgehip_ros_edgemap_device(self.ctx, int(first), int(count),
+                                                     *[C.c_void_p(x.data_ptr()) if x is not None else None for x in (points, keylines, kn)]))
+
+    def ros_edgemap_from(self, points=None, keylines=None, first=0):
+        """edgehip_ros_edgemap_from_device (test support only: a sentinel behind the records): uint8 torch tensors (count, cap, 12) / (count, cap, 52) become the stores' bytes."""
+        given = [x for x in (points, keylines) if x is not None]
+        count = given[0].shape[0]
+        for x, tail in ((points, (self.cap, 12)), (keylines, (self.cap, 52))):
+            if x is not None:
+                assert x.is_cuda and x.is_contiguous() and x.element_size() == 1 and tuple(x.shape) == (count,) + tail, tuple(x.shape)
+        self._ck(self.lib.edgehip_ros_edgemap_from_device(self.ctx, int(first), int(count),
+                                                          *[C.c_void_p(x.data_ptr()) if x is not None else None for x in (points, keylines)]))
+
+    def ros_export(self, seqs, k_prof, what):
+        """edgehip_ros_export: the OLD slot of the frame processed last, packed in-stream (no synchronisation) -> ticket."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.int32)
+        kp = np.ascontiguousarray(k_prof, dtype=np.float64)
+        assert kp.shape == seqs.shape
+        t = C.c_int(0)
+        self._ck(self.lib.edgehip_ros_export(self.ctx, len(seqs), seqs.ctypes.data_as(C.c_void_p), _dp(kp), int(what), C.byref(t)))
+        return (t.value, len(seqs), int(what))
+
+    def ros_export_fetch(self, ticket, kns, registered=True):
+        """edgehip_ros_export_fetch: enqueue the copies of kns[j] records per list (does not block); the arrays are valid after
+        ros_export_wait."""
+        tid, n, what = ticket
+        kns = np.ascontiguousarray(kns, dtype=np.int32)
+        assert len(kns) == n
+        pts = [np.zeros(self.cap, ROS_POINT_DTYPE) if what & ROS_POINTS else None for _ in range(n)]
+        kls = [np.zeros(self.cap, ROS_KEYLINE_DTYPE) if what & ROS_KEYLINES else None for _ in range(n)]
+        bufs = [b for b in pts + kls if b is not None]
+        if registered:
+            for b in bufs:
+                self._ck(self.lib.edgehip_register_host(C.c_void_p(b.ctypes.data), C.c_size_t(b.nbytes)))
+        pp = (C.c_void_p * n)(*[None if b is None else b.ctypes.data for b in pts])
+        pk = (C.c_void_p * n)(*[None if b is None else b.ctypes.data for b in kls])
+        self._ck(self.lib.edgehip_ros_export_fetch(self.ctx, tid, kns.ctypes.data_as(C.c_void_p), pp, pk))
+        return {"pts": pts, "kls": kls, "bufs": bufs, "kns": kns, "registered": registered, "ticket": ticket}
+
+    def ros_export_wait(self, fetched):
+        """edgehip_ros_export_wait.  With what ros_export_fetch returned: block until the copies have landed -> [(points, keylines)];
+        with a bare ticket: release it unfetched."""
+        if isinstance(fetched, tuple):
+            self._ck(self.lib.edgehip_ros_export_wait(self.ctx, fetched[0]))
+            return None
+        self._ck(self.lib.edgehip_ros_export_wait(self.ctx, fetched["ticket"][0]))
+        if fetched["registered"]:
+            for b in fetched["bufs"]:
+                self._ck(self.lib.edgehip_unregister_host(C.c_void_p(b.ctypes.data)))
+        return [(None if p is None else p[:k].copy(), None if q is None else q[:k].copy())
+                for p, q, k in zip(fetched["pts"], fetched["kls"], fetched["kns"])]
+
     def depth_surface_enable(self, surface=True, image_mode=0):
         """edgehip_depth_surface_enable; surface=None frees the products.  image_mode: 0 off, 1 getImgRho, 2 getImgRhoTriInterp."""
         if surface is None:

@@ -283,6 +283,16 @@ struct REBVOParameters {
     // handed over as PipeBuffer::depth_surface / depth_image.  Ignored while the fill is off.
     int DF_Surface = 0;
     int DF_DenseImage = 0;
+    // &EdgeMapOutput (ours): what the one output callback that ships with the reference builds per KeyLine, the ROS nodelet's
+    // (ros/src/rebvo_ros/src/rebvo_nodelet.cpp:176-212), packed on the device and handed to the output callback:
+    //   PointCloud = 1   PipeBuffer::point_cloud: the xyz float points of the rebvo_pcl cloud, with the buffer's K
+    //   KeylineMsg = 1   PipeBuffer::edge_map_msg: the Keyline.msg records of the EdgeMap message (52 bytes each, the ROS wire body)
+    //   KeyLineList = 0  the callback's ef list is left empty (KNum() == 0): the 168-byte KeyLine records are not brought to the host
+    // An absent section leaves the two products off and the list on.  Members of a batch group must agree; a group of ImuMode 1 / 2
+    // members delivers neither product (its K is known only after the frame behind has been enqueued) and is refused with them on.
+    int EM_PointCloud = 0;
+    int EM_KeylineMsg = 0;
+    int EM_KeyLineList = 1;
 };
 
 // Filter state SecondThread keeps in the IMU branch (reference include/rebvo/rebvo.h:239-290, same member names).
@@ -343,6 +353,17 @@ struct DepthImage {
     std::vector<float> rho, s_rho;
 };
 
+// (mirror only) &EdgeMapOutput PointCloud: n points, xyz[3 n] floats as a PointCloud2 with the fields "xyz" holds them (edgehip_ros_point).
+struct PointCloud {
+    int n = 0;
+    std::vector<float> xyz;
+};
+// (mirror only) &EdgeMapOutput KeylineMsg: n records of 52 bytes, the little-endian ROS wire body of `Keyline[] Keylines` (edgehip_ros_keyline).
+struct EdgeMapMsg {
+    int n = 0;
+    std::vector<uint8_t> records;
+};
+
 struct PipeBuffer {
     sspace *ss = nullptr;
     global_tracker *gt = nullptr;
@@ -369,6 +390,9 @@ struct PipeBuffer {
                                              // output callback; null when the fill is off or the delivery carries no KeyLines
     const DepthSurface *depth_surface = nullptr;   // (mirror only) &DepthFiller Surface = 1: from exactly depth_grid, same lifetime; else null
     const DepthImage *depth_image = nullptr;       // (mirror only) &DepthFiller DenseImage = 1 / 2: likewise
+    const PointCloud *point_cloud = nullptr;       // (mirror only) &EdgeMapOutput PointCloud = 1: from exactly this buffer's edge map and K, valid
+                                                   // during the output callback; null when off or the delivery carries no edge map
+    const EdgeMapMsg *edge_map_msg = nullptr;      // (mirror only) &EdgeMapOutput KeylineMsg = 1: likewise
 };
 
 namespace customCam {
@@ -411,6 +435,8 @@ class REBVO {
     std::map<const PipeBuffer *, std::unique_ptr<DepthGrid>> df_grids;   // &DepthFiller: the grid behind each ring buffer's depth_grid
     std::map<const PipeBuffer *, std::unique_ptr<DepthSurface>> df_surfs;   // ... and its surface / image (Surface, DenseImage)
     std::map<const PipeBuffer *, std::unique_ptr<DepthImage>> df_images;
+    std::map<const PipeBuffer *, std::unique_ptr<PointCloud>> em_clouds;   // &EdgeMapOutput: the products behind each ring buffer's pointers
+    std::map<const PipeBuffer *, std::unique_ptr<EdgeMapMsg>> em_msgs;
     BatchGroup *group = nullptr;
     int group_seat = -1;
     customCam::CustomCamPipeBuffer *cam_cur = nullptr;   // the buffer the application holds between request and releaseCustomCamBuffer

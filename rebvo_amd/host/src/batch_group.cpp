@@ -148,9 +148,14 @@ public:
 
     // AoS KeyLine lists for the members' callbacks, one export per step (edgehip_export_keylines right behind the step's
     // edgehip_process_frame): which seats it covers, and whether its copies have been enqueued yet
-    struct Export { long step = -1; int ticket = 0; std::vector<int32_t> seats; bool fetched = false; };
+    // ... and, with &EdgeMapOutput, the nodelet's cloud / records of the same edge maps (edgehip_ros_export, a ring of its own): `aos` / `ros` say
+    // which of the two tickets the step holds (KeyLineList = 0: no AoS lists)
+    struct Export { long step = -1; int ticket = 0; std::vector<int32_t> seats; bool fetched = false; bool aos = false;
+                    bool ros = false, ros_fetched = false; int ros_ticket = 0; };
     Export exp_of[4];              // [step & 3]
     // &DepthFiller (the same for every member): after a step, the grids of the edge maps its callbacks get (edgehip_depth_fill on the old slot)
+    int em_what = 0;               // &EdgeMapOutput PointCloud | KeylineMsg as EDGEHIP_ROS_* bits (the same for every member)
+    bool em_list = true;           // &EdgeMapOutput KeyLineList
     bool dfill = false;
     edgehip_depth_fill_params dfp{};
     edgehip_depth_surface_params dsp{};   // Surface / DenseImage (both 0: off)
@@ -161,6 +166,7 @@ public:
 
     void threadMain();
     int exportFetch(Export &ex, const std::vector<int32_t> &kn, const std::vector<edgehip_keyline *> &dst);
+    int rosFetch(Export &ex, const std::vector<PipeBuffer *> &buf);   // buf[j]: the PipeBuffer seat ex.seats[j]'s products land behind (null: none)
     void dropExports();
     bool gather(bool block, bool &any_running, bool &any_leaving);
     int upload(std::vector<double> &ts, int &slot);
@@ -210,11 +216,15 @@ bool REBVO::groupAttach() {
     edgehip_depth_surface_params dsp;
     std::memset(&dsp, 0, sizeof dsp);
     if (dfill) { dsp.surface = params.DF_Surface != 0; dsp.image_mode = params.DF_DenseImage; }
+    const int em_what = (params.EM_PointCloud ? EDGEHIP_ROS_POINTS : 0) | (params.EM_KeylineMsg ? EDGEHIP_ROS_KEYLINES : 0);
+    const bool em_list = params.EM_KeyLineList != 0;
     auto fail = [&](const std::string &msg) {
         last_error = msg;
         std::cout << last_error << "\n";
         return false;
     };
+    if (imu_mode && em_what)
+        return fail("REBVO(hip): &GPU BatchGroup with ImuMode 1 / 2 does not deliver &EdgeMapOutput PointCloud / KeylineMsg (a frame's K is known only after the next frame has been enqueued)");
     if (want < 1) return fail("REBVO(hip): &GPU BatchGroup needs BatchSize >= 1 (the number of objects that share the context)");
     if (params.GpuTrackerPrecision == 32 && (imu_mode || stereo))   // (edgehip_imu_enable / edgehip_set_stereo_rig refuse it too)
         return fail("REBVO(hip): &GPU TrackerPrecision=32 is Minimizer_RV<float>, the tracker of ImuMode 0 without a stereo pair");
@@ -257,6 +267,8 @@ bool REBVO::groupAttach() {
             if (rc == 0) rc = edgehip_set_stereo_rig(g->hip, BatchGroup::kPairSlot, kTCam2Pair, kRCam2Pair, 100.0);
         }
         if (rc == 0) rc = edgehip_set_nav_log(g->hip, BatchGroup::kNavLog);
+        g->em_what = em_what;
+        g->em_list = em_list;
         g->dfill = dfill;
         g->dfp = dfp;
         g->dsp = dsp;
@@ -301,6 +313,8 @@ bool REBVO::groupAttach() {
             return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same &DepthFiller parameters");
         if (std::memcmp(&g->dsp, &dsp, sizeof dsp) != 0)
             return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same &DepthFiller Surface and DenseImage");
+        if (g->em_what != em_what || g->em_list != em_list)
+            return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same &EdgeMapOutput PointCloud, KeylineMsg and KeyLineList");
     }
     std::unique_lock<std::mutex> lk(g->mut);
     if (g->started && g->attached >= g->cap) {
@@ -692,12 +706,23 @@ int REBVO::BatchGroup::launch(long step, const std::vector<double> &ts) {
         for (int i = 0; i < cap; i++) {
             Seat &st = seats[i];
             if (!st.running || !st.cf->haveCallBack() || st.frames < 2) continue;   // (frames counts this step's frame already)
-            if (!st.kl_pinned) pinKeyLines(st, true);
+            if (em_list && !st.kl_pinned) pinKeyLines(st, true);
             ex.seats.push_back(i);
         }
         if (!ex.seats.empty()) {
-            rc = edgehip_export_keylines(hip, (int)ex.seats.size(), ex.seats.data(), &ex.ticket);
-            if (rc != 0) return rc;
+            ex.aos = ex.ros = false;
+            if (em_list) {
+                rc = edgehip_export_keylines(hip, (int)ex.seats.size(), ex.seats.data(), &ex.ticket);
+                if (rc != 0) return rc;
+                ex.aos = true;
+            }
+            if (em_what) {   // the nodelet's products of the same edge maps, with the K their buffers carry: 1 for ImuMode 0 members (complete())
+                const std::vector<double> ks(ex.seats.size(), 1.0);
+                rc = edgehip_ros_export(hip, (int)ex.seats.size(), ex.seats.data(), ks.data(), em_what, &ex.ros_ticket);
+                if (rc != 0) return rc;
+                ex.ros = true;
+                ex.ros_fetched = false;
+            }
             ex.step = step;
             ex.fetched = false;
             if (dfill) {   // the grids of the same edge maps (the old slot), read back now: the next step's fill reuses the device grids
@@ -769,10 +794,45 @@ int REBVO::BatchGroup::exportFetch(Export &ex, const std::vector<int32_t> &kn, c
     return rc;
 }
 
+// The copies of a step's cloud / records into the storage behind the PipeBuffers they will be delivered with (kn = the buffer's KNum())
+int REBVO::BatchGroup::rosFetch(Export &ex, const std::vector<PipeBuffer *> &buf) {
+    const size_t n = ex.seats.size();
+    std::vector<int32_t> kn(n, 0);
+    std::vector<edgehip_ros_point *> pd(n, nullptr);
+    std::vector<edgehip_ros_keyline *> kd(n, nullptr);
+    for (size_t j = 0; j < n; j++) {
+        PipeBuffer *b = buf[j];
+        if (!b) continue;
+        REBVO *cf = seats[ex.seats[j]].cf;
+        kn[j] = b->ef->kn;
+        if (em_what & EDGEHIP_ROS_POINTS) {
+            std::unique_ptr<PointCloud> &pc = cf->em_clouds[b];
+            if (!pc) pc.reset(new PointCloud);
+            pc->n = kn[j];
+            pc->xyz.resize(3 * (size_t)kn[j]);
+            pd[j] = reinterpret_cast<edgehip_ros_point *>(pc->xyz.data());
+        }
+        if (em_what & EDGEHIP_ROS_KEYLINES) {
+            std::unique_ptr<EdgeMapMsg> &em = cf->em_msgs[b];
+            if (!em) em.reset(new EdgeMapMsg);
+            em->n = kn[j];
+            em->records.resize(sizeof(edgehip_ros_keyline) * (size_t)kn[j]);
+            kd[j] = reinterpret_cast<edgehip_ros_keyline *>(em->records.data());
+        }
+    }
+    const int rc = edgehip_ros_export_fetch(hip, ex.ros_ticket, kn.data(), pd.data(), kd.data());
+    if (rc == 0) ex.ros_fetched = true;
+    return rc;
+}
+
 // Every export still outstanding is waited for (or dropped): before KeyLine arrays are unpinned, a copy must not be on its way into them.
 void REBVO::BatchGroup::dropExports() {
     for (Export &ex : exp_of)
-        if (ex.step >= 0) { (void)edgehip_export_wait(hip, ex.ticket); ex.step = -1; }
+        if (ex.step >= 0) {
+            if (ex.aos) (void)edgehip_export_wait(hip, ex.ticket);
+            if (ex.ros) (void)edgehip_ros_export_wait(hip, ex.ros_ticket);
+            ex.step = -1;
+        }
 }
 
 // Hand the camera buffers of the step launched last back as soon as the copies into its slot have read them (the frames are still
@@ -845,6 +905,8 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
             ob.depth_grid = nullptr;
             ob.depth_surface = nullptr;
             ob.depth_image = nullptr;
+            ob.point_cloud = nullptr;
+            ob.edge_map_msg = nullptr;
             if (dfill && cf->haveCallBack() && cb_depth > 1 && in_export(i)) {   // the grid of exactly the lists exported with this step
                 std::unique_ptr<DepthGrid> &gd = cf->df_grids[&ob];
                 if (!gd) gd.reset(new DepthGrid);
@@ -869,6 +931,8 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
                 if (!in_export(i)) ob.ef->kn = 0;
             } else if (cf->haveCallBack() && newest - step >= 2) {
                 ob.ef->kn = 0;
+            } else if (cf->haveCallBack() && !em_list) {
+                ob.ef->kn = 0;   // (REBVO_GROUP_CB_DEPTH=1 with KeyLineList = 0: no list; the nodelet's products need the pipelined delivery)
             } else if (cf->haveCallBack()) {
                 if (!st.kl_pinned) pinKeyLines(st, true);
                 cb_seq.push_back(i);
@@ -912,31 +976,50 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
     if (have_ex) {
         // this step's export: the lists of the frames about to be delivered.  Normally its copies were enqueued one completion ago
         // (below) and have landed under the steps since; a step completed right behind its launch enqueues them now.
-        if (!ex.fetched) {
+        if (ex.aos && !ex.fetched) {
             std::vector<int32_t> kn(ex.seats.size(), 0);
             std::vector<edgehip_keyline *> dst(ex.seats.size(), nullptr);
             for (size_t j = 0; j < ex.seats.size(); j++)
                 if (PipeBuffer *ob = deliver[ex.seats[j]]) { kn[j] = ob->ef->kn; dst[j] = reinterpret_cast<edgehip_keyline *>(ob->ef->kl.data()); }
             rc = exportFetch(ex, kn, dst);
         }
-        const int rw = edgehip_export_wait(hip, ex.ticket);
+        if (ex.ros && !ex.ros_fetched && rc == 0) {
+            std::vector<PipeBuffer *> buf(ex.seats.size(), nullptr);
+            for (size_t j = 0; j < ex.seats.size(); j++) buf[j] = deliver[ex.seats[j]];
+            rc = rosFetch(ex, buf);
+        }
+        if (ex.aos) { const int rw = edgehip_export_wait(hip, ex.ticket); if (rc == 0) rc = rw; }
+        if (ex.ros) { const int rw = edgehip_ros_export_wait(hip, ex.ros_ticket); if (rc == 0) rc = rw; }
         ex.step = -1;
-        if (rc == 0) rc = rw;
         if (rc != 0) {
             std::cout << "\nREBVO: KeyLine export failed: " << edgehip_last_error() << "\n";
             for (int seat : ex.seats) if (deliver[seat]) deliver[seat]->ef->kn = 0;
+        } else {
+            for (int seat : ex.seats) {
+                PipeBuffer *ob = deliver[seat];
+                if (!ob) continue;
+                REBVO *cf = seats[seat].cf;
+                if (ex.ros && (em_what & EDGEHIP_ROS_POINTS) && cf->em_clouds.count(ob)) ob->point_cloud = cf->em_clouds[ob].get();
+                if (ex.ros && (em_what & EDGEHIP_ROS_KEYLINES) && cf->em_msgs.count(ob)) ob->edge_map_msg = cf->em_msgs[ob].get();
+                if (!em_list) ob->ef->kn = 0;   // &EdgeMapOutput KeyLineList = 0: the callback's list stays empty
+            }
         }
     }
     {   // the NEXT step's export (already packed if that step has been launched): its lists belong to the frames whose records were just
         // read — the lengths are known now, the destinations are these frames' PipeBuffers — so its copies go out at once and run under
         // the steps in flight
         Export &nx = exp_of[(step + 1) & 3];
-        if (rc == 0 && nx.step == step + 1 && !nx.fetched) {
+        if (rc == 0 && nx.step == step + 1 && nx.aos && !nx.fetched) {
             std::vector<int32_t> kn(nx.seats.size(), 0);
             std::vector<edgehip_keyline *> dst(nx.seats.size(), nullptr);
             for (size_t j = 0; j < nx.seats.size(); j++)
                 if (PipeBuffer *nb = mine[nx.seats[j]]) { kn[j] = nb->ef->kn; dst[j] = reinterpret_cast<edgehip_keyline *>(nb->ef->kl.data()); }
             rc = exportFetch(nx, kn, dst);
+        }
+        if (rc == 0 && nx.step == step + 1 && nx.ros && !nx.ros_fetched) {
+            std::vector<PipeBuffer *> buf(nx.seats.size(), nullptr);
+            for (size_t j = 0; j < nx.seats.size(); j++) buf[j] = mine[nx.seats[j]];
+            rc = rosFetch(nx, buf);
         }
     }
     for (int i = 0; i < cap; i++) {   // (PipeBuffer::img, the grey image a callback may look at, is formed by the member's output thread)
@@ -1174,6 +1257,42 @@ extern "C" int rebvo_group_depth_surface_selftest(const char *config_file) {
     if (!e.Init()) return 5;                                                          // the same keys: the group starts
     a.CleanUp();
     e.CleanUp();
+    return 0;
+}
+
+// Members of one group with other &EdgeMapOutput keys are refused at Init() (GPU test hook): 0 = as expected
+extern "C" int rebvo_group_edgemap_selftest(const char *config_file) {
+    using namespace rebvo;
+    REBVO proto(config_file);
+    if (!proto.isInitOk()) return 1;
+    REBVOParameters p = proto.getParams();
+    p.CameraType = 3; p.ImuMode = 0; p.StereoAvaiable = false;
+    p.GpuBatchGroup = "em_selftest";
+    p.GpuBatchSize = 2;
+    p.EM_PointCloud = 1; p.EM_KeylineMsg = 0; p.EM_KeyLineList = 1;
+    REBVO a(p);
+    if (!a.Init()) return 2;
+    for (int k = 0; k < 3; k++) {
+        REBVOParameters q = p;
+        if (k == 0) q.EM_PointCloud = 0;
+        if (k == 1) q.EM_KeylineMsg = 1;
+        if (k == 2) q.EM_KeyLineList = 0;
+        REBVO b(q);
+        if (b.Init() || b.lastError().find("EdgeMapOutput") == std::string::npos) return 3 + k;
+    }
+    REBVO e(p);
+    if (!e.Init()) return 6;   // the same keys: the group starts
+    a.CleanUp();
+    e.CleanUp();
+    return 0;
+}
+
+// The three &EdgeMapOutput keys as the GlobalConfig parser reads them (CPU test hook, needs no device): out = PointCloud, KeylineMsg, KeyLineList
+extern "C" int rebvo_edgemap_output_config(const char *config_file, int *out) {
+    rebvo::REBVO proto(config_file);
+    if (!proto.isInitOk()) return 1;
+    const rebvo::REBVOParameters p = proto.getParams();
+    out[0] = p.EM_PointCloud; out[1] = p.EM_KeylineMsg; out[2] = p.EM_KeyLineList;
     return 0;
 }
 

@@ -313,6 +313,9 @@ REBVO::REBVO(const char *configFile)
     config.get("DepthFiller", "Discard", p.DF_Discard, false);
     config.get("DepthFiller", "Surface", p.DF_Surface, false);
     config.get("DepthFiller", "DenseImage", p.DF_DenseImage, false);
+    config.get("EdgeMapOutput", "PointCloud", p.EM_PointCloud, false);    // optional section, ours
+    config.get("EdgeMapOutput", "KeylineMsg", p.EM_KeylineMsg, false);
+    config.get("EdgeMapOutput", "KeyLineList", p.EM_KeyLineList, false);
     construct();
 }
 
@@ -466,6 +469,8 @@ bool REBVO::Init() {
         rc = edgehip_set_slot_camera(hip, 3, params.pp_x_stereo, params.pp_y_stereo, params.z_f_x_stereo, params.z_f_y_stereo);
         if (rc == 0 && params.ImuMode == 0) rc = edgehip_set_stereo_rig(hip, 3, kTCam2Pair, kRCam2Pair, 100.0);
     }
+    if (rc == 0 && (params.EM_PointCloud || params.EM_KeylineMsg))   // &EdgeMapOutput: the stores the output callback's products are packed into
+        rc = edgehip_ros_enable(hip, (params.EM_PointCloud ? EDGEHIP_ROS_POINTS : 0) | (params.EM_KeylineMsg ? EDGEHIP_ROS_KEYLINES : 0));
     if (rc != 0) {   // no CPU fallback: fail loudly
         last_error = std::string("REBVO(hip): edgehip_create failed: ") + edgehip_last_error();
         std::cout << last_error << "\n";
@@ -637,7 +642,38 @@ void REBVO::TrackThread(REBVO *cf) {
         // ---- hand the PREVIOUS frame to the output thread, with its edge map as the tracker left it ----
         if (old_buf) {
             const bool want = cf->haveCallBack();
-            if (want) {
+            const int em_what = (cf->params.EM_PointCloud ? EDGEHIP_ROS_POINTS : 0) | (cf->params.EM_KeylineMsg ? EDGEHIP_ROS_KEYLINES : 0);
+            old_buf->point_cloud = nullptr;
+            old_buf->edge_map_msg = nullptr;
+            if (want && em_what && rc == 0) {
+                // &EdgeMapOutput: the nodelet's two products of the same edge map, packed on the device with this buffer's K.  (A single
+                // object synchronises for its callback anyway, so it packs into the stores and downloads; a batch group uses the ring.)
+                const int so = (slot + 2) % 3;
+                const double K = old_buf->K;
+                std::unique_ptr<PointCloud> &pc = cf->em_clouds[old_buf];
+                std::unique_ptr<EdgeMapMsg> &em = cf->em_msgs[old_buf];
+                if (!pc) pc.reset(new PointCloud);
+                if (!em) em.reset(new EdgeMapMsg);
+                const size_t capn = (size_t)cf->params.MaxPoints;
+                if (em_what & EDGEHIP_ROS_POINTS) pc->xyz.resize(3 * capn);
+                if (em_what & EDGEHIP_ROS_KEYLINES) em->records.resize(sizeof(edgehip_ros_keyline) * capn);
+                int32_t kn_em = 0;
+                rc = edgehip_ros_pack(cf->hip, so, &K);
+                if (rc == 0)
+                    rc = edgehip_download_ros_edgemap(cf->hip, 0, (em_what & EDGEHIP_ROS_POINTS) ? reinterpret_cast<edgehip_ros_point *>(pc->xyz.data()) : nullptr,
+                                                      (em_what & EDGEHIP_ROS_KEYLINES) ? reinterpret_cast<edgehip_ros_keyline *>(em->records.data()) : nullptr, &kn_em);
+                if (rc != 0) {
+                    std::cout << "\nREBVO: edgehip_ros_pack failed: " << edgehip_last_error() << "\n";
+                    failed = true;
+                } else {
+                    if (em_what & EDGEHIP_ROS_POINTS) { pc->n = kn_em; pc->xyz.resize(3 * (size_t)kn_em); old_buf->point_cloud = pc.get(); }
+                    if (em_what & EDGEHIP_ROS_KEYLINES) { em->n = kn_em; em->records.resize(sizeof(edgehip_ros_keyline) * (size_t)kn_em); old_buf->edge_map_msg = em.get(); }
+                }
+                rc = 0;
+            }
+            if (want && !cf->params.EM_KeyLineList) {
+                old_buf->ef->kn = 0;   // &EdgeMapOutput KeyLineList = 0: the callback's list stays empty, nothing of it crosses the link
+            } else if (want) {
                 const int so = (slot + 2) % 3;   // ring of 3: the slot before `slot`
                 int32_t kn = 0;
                 const int32_t seq0 = 0;
