@@ -1324,7 +1324,11 @@ __global__ __launch_bounds__(256) void k_stereo_match(StereoArgs a) {
         const float2 pm = k.p_m[i], mm = k.m_m[i];
         const float nm = k.n_m[i];
         const double rho = k.rho[i], s_rho = k.s_rho[i];
-        const double min_rho = fmax(rho - s_rho, 1e-3), max_rho = fmin(rho + s_rho, 20.0);   // RHO_MIN, RHO_MAX
+        // std::max(k.rho - k.s_rho, RHO_MIN), std::min(k.rho + k.s_rho, RHO_MAX) (edge_tracker.cpp:474-475) return their FIRST argument when
+        // the comparison is false: a NaN bound goes through (fmax / fmin would drop it), q1min is NaN, norm_t > 1e-6 is false and the
+        // KeyLine searches across its edge from pi0 = NaN: it matches nothing.
+        const double lo = rho - s_rho, hi = rho + s_rho;
+        const double min_rho = lo < 1e-3 ? 1e-3 : lo, max_rho = 20.0 < hi ? 20.0 : hi;   // RHO_MIN, RHO_MAX
         double q1[2][3];
 #pragma unroll
         for (int e = 0; e < 2; e++) {
@@ -1365,6 +1369,10 @@ __global__ __launch_bounds__(256) void k_stereo_match(StereoArgs a) {
         float2 pm_match = make_float2(0.f, 0.f);
         for (int t = (int)dq_min; (double)t < dq_max; t++) {
             const float fx = (float)(t_x * (double)(float)t + pi0x), fy = (float)(t_y * (double)(float)t + pi0y);
+            // Image::GetIndexRC (image.h:121-126) converts round(x) to int: a NaN becomes INT_MIN on x86-64, "out of border".  The rule is
+            // spelled out here so that it does not rest on what the hardware conversion makes of a NaN (measured on MI355X: INT_MAX, which is
+            // out of the image as well; +-inf and values beyond int saturate there and are INT_MIN on x86-64: out either way).
+            if (fx != fx || fy != fy) continue;
             const int xi = round_half_away_i(fx), yi = round_half_away_i(fy);
             if (xi >= a.w || yi >= a.h || xi < 0 || yi < 0) continue;
             const int j = mask[(size_t)yi * a.w + xi];

@@ -5,7 +5,7 @@ import numpy as np
 def to_edgehip_kl(kl):
     """oracle KEYLINE_DTYPE and edgehip KEYLINE_DTYPE are the same 168-byte layout."""
     from rebvo_amd import edgehip
-    return np.frombuffer(np.ascontiguousarray(kl).tobytes(), dtype=edgehip.KEYLINE_DTYPE).copy()
+    return np.ascontiguousarray(kl).view(edgehip.KEYLINE_DTYPE).copy()          # (a view: an empty list stays a list)
 
 
 def oracle_pair(w, h, n_warm, seq="billboard", seed=None, traj_seed=None, frames=None, **over):
