@@ -426,7 +426,7 @@ int edgehip_download_keylines_batch(edgehip_ctx *ctx, int slot, int n, const int
  *   edgehip_export_fetch     once the caller knows the lists' lengths (kn[j] = edgehip_nav::kn of frame k-1 for seqs[j]): enqueues the copies
  *                            of exactly kn[j] records into dst[j] on a stream of their own (page-locked destinations — edgehip_register_host —
  *                            are written by DMA under the frames that follow; pageable ones work, slower).  Does not block.
- *   edgehip_export_wait      blocks until the ticket's copies have landed and releases the ticket (never fetched: just releases it).
+ *   edgehip_export_wait      blocks until the ticket's copies have landed and releases the ticket (never fetched: waits for the pack itself, as edgehip_ros_export_wait does).
  * Record for record what edgehip_download_keylines_batch returns for the same slot at the same point. */
 int edgehip_export_keylines(edgehip_ctx *ctx, int n, const int32_t *seqs, int *ticket_out);
 int edgehip_export_fetch(edgehip_ctx *ctx, int ticket, const int32_t *kn, edgehip_keyline *const *dst);

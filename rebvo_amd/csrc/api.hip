@@ -670,17 +670,8 @@ int edgehip_destroy(edgehip_ctx *c) {
         delete c->prof;
     }
     if (c->aos_dev) { (void)hipFree(c->aos_dev); (void)hipHostFree(c->aos_host); (void)hipFree(c->aos_req_dev); (void)hipHostFree(c->aos_req_host); }
-    if (c->kl_export) {
-        auto *x = c->kl_export;
-        if (x->stream) { (void)hipStreamSynchronize(x->stream); (void)hipStreamDestroy(x->stream); }
-        for (hipEvent_t e : x->ev_pack) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : x->ev_done) if (e) (void)hipEventDestroy(e);
-        if (x->dev) (void)hipFree(x->dev);
-        if (x->req) (void)hipHostFree(x->req);
-        for (edgehip_keyline *h : x->host) if (h) (void)hipHostFree(h);
-        delete x;
-        c->kl_export = nullptr;
-    }
+    c->kl_ring.close();
+    c->ros_ring.close();
     if (c->stream_log) {
         (void)hipStreamSynchronize(c->stream_log); (void)hipStreamDestroy(c->stream_log); (void)hipEventDestroy(c->ev_log);
         for (hipEvent_t e : c->ev_log_ring) if (e) (void)hipEventDestroy(e);
@@ -1316,133 +1307,180 @@ int edgehip_download_keylines_batch(edgehip_ctx *c, int slot, int n, const int32
     return 0;
 }
 
-// ---- output callbacks at full pipeline depth (round 6) ----------------------------------------------------------------------------
+// ---- output callbacks at full pipeline depth: the staging ring (export_ring.h) ---------------------------------------------------
+int ExportRing::open(bool highest_priority) {
+    if (stream) return 0;
+    int least = 0, greatest = 0;
+    if (!(highest_priority && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest &&
+          hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, greatest) == hipSuccess)) {
+        (void)hipGetLastError();
+        EH_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    }
+    for (int i = 0; i < R; i++) {
+        EH_CHECK(hipEventCreateWithFlags(&ev_pack[i], hipEventDisableTiming));
+        EH_CHECK(hipEventCreateWithFlags(&ev_done[i], hipEventDisableTiming));
+    }
+    return 0;
+}
+
+void ExportRing::drop_memory() {
+    if (dev) (void)hipFree(dev);
+    if (rows) (void)hipHostFree(rows);
+    for (uint8_t *&h : host) if (h) { (void)hipHostFree(h); h = nullptr; }
+    dev = rows = nullptr;
+    n_cap = 0;
+    entry_bytes = row_bytes = 0;
+}
+
+int ExportRing::reserve(edgehip_ctx *c, const char *who, int n, size_t entry, size_t row) {
+    for (const Ticket &k : t)
+        if (k.id >= 0) { set_error(std::string(who) + ": a larger request than before while tickets are outstanding"); return EDGEHIP_ERR_STATE; }
+    EH_CHECK(hipStreamSynchronize(c->stream));
+    EH_CHECK(hipStreamSynchronize(stream));
+    drop_memory();
+    entry = (entry + 15) & ~(size_t)15;
+    row = (row + 15) & ~(size_t)15;
+    void *d = nullptr, *h = nullptr;
+    if (hipMalloc(&d, entry * R) != hipSuccess || hipHostMalloc(&h, row * R, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        if (d) (void)hipFree(d);
+        set_error(std::string(who) + ": staging alloc failed");
+        return EDGEHIP_ERR_MEMORY;
+    }
+    dev = (uint8_t *)d;
+    rows = (uint8_t *)h;
+    // on the stream the packing kernel follows on (hipMemset runs on the null stream, which a non-blocking stream does not wait for)
+    const hipError_t z = hipMemsetAsync(dev, 0, entry * R, c->stream);
+    if (z != hipSuccess) drop_memory();
+    EH_CHECK(z);
+    n_cap = n;
+    entry_bytes = entry;
+    row_bytes = row;
+    return 0;
+}
+
+int ExportRing::claim(const char *who, int *e) {
+    *e = (int)(next % R);
+    if (t[*e].id >= 0) { set_error(std::string(who) + ": four tickets outstanding (the wait call of a ticket releases it)"); return EDGEHIP_ERR_STATE; }
+    return 0;
+}
+
+int ExportRing::commit(edgehip_ctx *c, int e, int slot, int n, int what, int *ticket_out) {
+    EH_CHECK(hipEventRecord(ev_pack[e], c->stream));
+    if (int er = slot_read_done(c, slot)) return er;   // the frame after next detects into this slot on the stage-A stream: not before the lists are out
+    t[e] = Ticket();
+    t[e].id = next;
+    t[e].n = n;
+    t[e].what = what;
+    *ticket_out = (int)(next & 0x7fffffff);
+    next++;
+    return 0;
+}
+
+ExportRing::Ticket *ExportRing::find(int ticket, int *e) {
+    for (*e = 0; *e < R; ++*e)
+        if (t[*e].id >= 0 && (int)(t[*e].id & 0x7fffffff) == ticket) return &t[*e];
+    return nullptr;
+}
+
+int ExportRing::fetch(const char *who, int e, const std::vector<Copy> &copies) {
+    // the page-locked mirror for pageable destinations first: once a copy is enqueued nothing below can fail for lack of memory
+    std::vector<char> direct(copies.size());
+    bool mirror = false;
+    for (size_t i = 0; i < copies.size(); i++) {
+        direct[i] = host_registered(copies[i].dst, copies[i].bytes) ? 1 : 0;
+        mirror |= !direct[i];
+    }
+    if (mirror && !host[e]) {
+        void *q = nullptr;
+        if (hipHostMalloc(&q, entry_bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); set_error(std::string(who) + ": pinned alloc failed"); return EDGEHIP_ERR_MEMORY; }
+        host[e] = (uint8_t *)q;
+    }
+    EH_CHECK(hipStreamWaitEvent(stream, ev_pack[e], 0));
+    t[e].staged.clear();
+    for (size_t i = 0; i < copies.size(); i++) {
+        const Copy &cp = copies[i];
+        if (!direct[i]) t[e].staged.push_back(cp);   // through the mirror, and a host copy in release()
+        EH_CHECK(hipMemcpyAsync(direct[i] ? cp.dst : host[e] + cp.off, entry(e) + cp.off, cp.bytes, hipMemcpyDeviceToHost, stream));
+    }
+    EH_CHECK(hipEventRecord(ev_done[e], stream));
+    t[e].fetched = true;
+    return 0;
+}
+
+int ExportRing::release(int e) {
+    if (t[e].fetched) {
+        EH_CHECK(hipEventSynchronize(ev_done[e]));
+        for (const Copy &cp : t[e].staged) memcpy(cp.dst, host[e] + cp.off, cp.bytes);
+    } else {
+        // never fetched: the packing kernel reads the entry's request row in place and writes its device bytes, so the entry is free only
+        // behind it — the next export into it may name other sequences
+        EH_CHECK(hipEventSynchronize(ev_pack[e]));
+    }
+    t[e] = Ticket();
+    return 0;
+}
+
+void ExportRing::close() {
+    if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); stream = nullptr; }
+    for (int i = 0; i < R; i++) {
+        if (ev_pack[i]) (void)hipEventDestroy(ev_pack[i]);
+        if (ev_done[i]) (void)hipEventDestroy(ev_done[i]);
+        ev_pack[i] = ev_done[i] = nullptr;
+    }
+    drop_memory();
+}
+
 // What a callback receives of frame k-1 is its edge map as frame k's tracking left it (rebvo_second_t.cpp:622-623; rebvo_third_t.cpp:174):
 // the OLD slot of the frame processed last.  edgehip_download_keylines_batch reads it behind a synchronisation of both frame streams,
 // and the frame after next detects into that slot — so a caller that wanted KeyLines could keep only one frame in flight.  Here the
-// lists are packed in-stream, right behind the frame, into a staging ring of their own; the slot is free again as far as callbacks go,
-// the copies to the host run on a stream of their own under the frames that follow, and nothing synchronises the frame streams.
+// lists go through c->kl_ring.
 int edgehip_export_keylines(edgehip_ctx *c, int n, const int32_t *seqs, int *ticket_out) {
     EH_ENTER(c);
     if (!c || n < 1 || !seqs || !ticket_out) { set_error("export_keylines: bad argument"); return EDGEHIP_ERR_ARG; }
     for (int j = 0; j < n; j++)
         if (int e = check_seq(c, seqs[j])) return e;
     if (c->frames_seen < 2 || c->frame_slot < 0) { set_error("export_keylines: needs two processed frames (the old slot of a frame pair)"); return EDGEHIP_ERR_STATE; }
-    if (!c->kl_export) c->kl_export = new edgehip_ctx::KlExport;
-    auto *x = c->kl_export;
-    constexpr int R = edgehip_ctx::KlExport::R;
+    ExportRing &x = c->kl_ring;
     const size_t cap = (size_t)c->plan.cap;
-    if (!x->stream) {
-        // Which hardware queue the copies land on decides what waits behind them (HIP maps a context's streams onto four queues per priority
-        // class; stage_imu.hip imu_stream_create).  Measured with eight cameras that take every frame's KeyLines: ImuMode 0 — default
-        // priority 16.8-17.2 k frames/s, highest 5.6 k (the copies' event waits stall the frame streams); ImuMode 2, where the frame streams
-        // are idle half the step under the scale filter — default 5.5-6.1 k, highest 11.3 k.  So: a queue class of its own beside the IMU branch.
-        int least = 0, greatest = 0;
-        if (!(c->imu_enabled && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest &&
-              hipStreamCreateWithPriority(&x->stream, hipStreamNonBlocking, greatest) == hipSuccess)) {
-            (void)hipGetLastError();
-            EH_CHECK(hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking));
-        }
-        for (int i = 0; i < R; i++) {
-            EH_CHECK(hipEventCreateWithFlags(&x->ev_pack[i], hipEventDisableTiming));
-            EH_CHECK(hipEventCreateWithFlags(&x->ev_done[i], hipEventDisableTiming));
-        }
-    }
-    if (n > x->n_cap) {   // staging for n lists per ticket (grown, never shrunk): only with no ticket outstanding
-        for (auto &t : x->t)
-            if (t.id >= 0) { set_error("export_keylines: more lists than before while tickets are outstanding"); return EDGEHIP_ERR_STATE; }
-        EH_CHECK(hipStreamSynchronize(c->stream));
-        EH_CHECK(hipStreamSynchronize(x->stream));
-        if (x->dev) { (void)hipFree(x->dev); x->dev = nullptr; }
-        if (x->req) { (void)hipHostFree(x->req); x->req = nullptr; }
-        for (edgehip_keyline *&h : x->host) if (h) { (void)hipHostFree(h); h = nullptr; }
-        x->n_cap = 0;
-        void *q = nullptr;
-        if (hipMalloc(&q, sizeof(edgehip_keyline) * cap * n * R) != hipSuccess) { (void)hipGetLastError(); set_error("export_keylines: staging alloc failed"); return EDGEHIP_ERR_MEMORY; }
-        x->dev = (edgehip_keyline *)q;
-        EH_CHECK(hipMemsetAsync(x->dev, 0, sizeof(edgehip_keyline) * cap * n * R, c->stream));   // on the stream the packing kernel follows on (hipMemset
-                                                                                                   // runs on the null stream, which a non-blocking stream does not wait for)
-        if (hipHostMalloc(&q, sizeof(int32_t) * n * R, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); set_error("export_keylines: pinned alloc failed"); return EDGEHIP_ERR_MEMORY; }
-        x->req = (int32_t *)q;
-        x->n_cap = n;
-    }
-    const int e = (int)(x->next % R);
-    if (x->t[e].id >= 0) { set_error("export_keylines: four tickets outstanding (edgehip_export_wait releases one)"); return EDGEHIP_ERR_STATE; }
+    // Which hardware queue the copies land on decides what waits behind them (HIP maps a context's streams onto four queues per priority
+    // class; stage_imu.hip imu_stream_create).  Measured with eight cameras that take every frame's KeyLines: ImuMode 0 — default
+    // priority 16.8-17.2 k frames/s, highest 5.6 k (the copies' event waits stall the frame streams); ImuMode 2, where the frame streams
+    // are idle half the step under the scale filter — default 5.5-6.1 k, highest 11.3 k.  So: a queue class of its own beside the IMU branch.
+    if (int er = x.open(c->imu_enabled)) return er;
+    if (n > x.n_cap) { if (int er = x.reserve(c, "export_keylines", n, sizeof(edgehip_keyline) * cap * n, sizeof(int32_t) * n)) return er; }
+    int e = 0;
+    if (int er = x.claim("export_keylines", &e)) return er;
     const int so = (c->frame_slot - 1 + c->ring_slots) % c->ring_slots;
     if (int er = rot_materialize_enqueue(c, so)) return er;   // a slot the whole-frame driver rotated out of place (ctx.h: fuse_match)
-    int32_t *req = x->req + (size_t)e * x->n_cap;
+    int32_t *req = (int32_t *)x.row(e);
     for (int j = 0; j < n; j++) req[j] = seqs[j];
     hipLaunchKernelGGL(k_pack_keylines, dim3((unsigned)((cap + 255) / 256), (unsigned)n), dim3(256), 0, c->stream, kldev(c, so),
-                       c->kn_slot + (size_t)so * c->plan.nseq, req, (int32_t *)nullptr, x->dev + (size_t)e * x->n_cap * cap, (int)cap);
+                       c->kn_slot + (size_t)so * c->plan.nseq, req, (int32_t *)nullptr, (edgehip_keyline *)x.entry(e), (int)cap);
     EH_LAUNCH_CHECK();
-    EH_CHECK(hipEventRecord(x->ev_pack[e], c->stream));
-    if (c->stream_a != c->stream) {   // the frame after next detects into this slot on the stage-A stream: not before the lists are out
-        EH_CHECK(hipEventRecord(c->ev_use[so], c->stream));
-        c->use_valid[so] = true;
-    }
-    x->t[e].id = x->next;
-    x->t[e].n = n;
-    x->t[e].fetched = false;
-    *ticket_out = (int)(x->next & 0x7fffffff);
-    x->next++;
-    return 0;
-}
-
-static edgehip_ctx::KlExport::Ticket *export_ticket(edgehip_ctx *c, int ticket, int &e) {
-    auto *x = c ? c->kl_export : nullptr;
-    if (!x) return nullptr;
-    for (e = 0; e < edgehip_ctx::KlExport::R; e++)
-        if (x->t[e].id >= 0 && (int)(x->t[e].id & 0x7fffffff) == ticket) return &x->t[e];
-    return nullptr;
+    return x.commit(c, e, so, n, 0, ticket_out);
 }
 
 int edgehip_export_fetch(edgehip_ctx *c, int ticket, const int32_t *kn, edgehip_keyline *const *dst) {
     EH_ENTER(c);
     int e = 0;
-    auto *t = export_ticket(c, ticket, e);
+    auto *t = c->kl_ring.find(ticket, &e);
     if (!t || !kn || !dst) { set_error("export_fetch: unknown ticket or null argument"); return EDGEHIP_ERR_ARG; }
     if (t->fetched) { set_error("export_fetch: ticket already fetched"); return EDGEHIP_ERR_STATE; }
-    auto *x = c->kl_export;
     const size_t cap = (size_t)c->plan.cap;
-    for (int j = 0; j < t->n; j++)
-        if (kn[j] < 0 || (size_t)kn[j] > cap || (kn[j] > 0 && !dst[j])) { set_error("export_fetch: KeyLine count beyond the capacity, or null destination"); return EDGEHIP_ERR_ARG; }
-    EH_CHECK(hipStreamWaitEvent(x->stream, x->ev_pack[e], 0));
-    t->staged_dst.assign(t->n, nullptr);
-    t->staged_kn.assign(t->n, 0);
+    std::vector<ExportRing::Copy> copies;
     for (int j = 0; j < t->n; j++) {
-        if (kn[j] <= 0) continue;
-        edgehip_keyline *to = dst[j];
-        if (!host_registered(dst[j], sizeof(edgehip_keyline) * kn[j])) {
-            // a pageable destination: through a page-locked staging list of the ticket, and a host copy in edgehip_export_wait
-            if (!x->host[e]) {
-                void *q = nullptr;
-                if (hipHostMalloc(&q, sizeof(edgehip_keyline) * cap * x->n_cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); set_error("export_fetch: pinned alloc failed"); return EDGEHIP_ERR_MEMORY; }
-                x->host[e] = (edgehip_keyline *)q;
-            }
-            to = x->host[e] + (size_t)j * cap;
-            t->staged_dst[j] = dst[j];
-            t->staged_kn[j] = kn[j];
-        }
-        EH_CHECK(hipMemcpyAsync(to, x->dev + ((size_t)e * x->n_cap + j) * cap, sizeof(edgehip_keyline) * kn[j], hipMemcpyDeviceToHost, x->stream));
+        if (kn[j] < 0 || (size_t)kn[j] > cap || (kn[j] > 0 && !dst[j])) { set_error("export_fetch: KeyLine count beyond the capacity, or null destination"); return EDGEHIP_ERR_ARG; }
+        if (kn[j] > 0) copies.push_back({dst[j], sizeof(edgehip_keyline) * cap * j, sizeof(edgehip_keyline) * kn[j]});
     }
-    EH_CHECK(hipEventRecord(x->ev_done[e], x->stream));
-    t->fetched = true;
-    return 0;
+    return c->kl_ring.fetch("export_fetch", e, copies);
 }
 
 int edgehip_export_wait(edgehip_ctx *c, int ticket) {
     EH_ENTER(c);
     int e = 0;
-    auto *t = export_ticket(c, ticket, e);
-    if (!t) { set_error("export_wait: unknown ticket"); return EDGEHIP_ERR_ARG; }
-    if (t->fetched) {
-        EH_CHECK(hipEventSynchronize(c->kl_export->ev_done[e]));
-        for (int j = 0; j < t->n; j++)
-            if (t->staged_dst[j]) memcpy(t->staged_dst[j], c->kl_export->host[e] + (size_t)j * c->plan.cap, sizeof(edgehip_keyline) * t->staged_kn[j]);
-    }
-    t->id = -1;          // (a ticket that was never fetched is simply dropped: its staging entry is free again)
-    t->fetched = false;
-    return 0;
+    if (!c->kl_ring.find(ticket, &e)) { set_error("export_wait: unknown ticket"); return EDGEHIP_ERR_ARG; }
+    return c->kl_ring.release(e);
 }
 
 int edgehip_upload_keylines(edgehip_ctx *c, int seq, int slot, const edgehip_keyline *kl, int32_t kn, const int32_t *mask, float retuned) {
@@ -1621,4 +1659,3 @@ int edgehip_profile_read(edgehip_ctx *c, double *ms, int64_t *calls) {
 
 }  // extern "C"
 
-bool edgehip::host_range_registered(const void *p, size_t bytes) { return host_registered(p, bytes); }

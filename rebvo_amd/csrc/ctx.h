@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include <string>
 #include <map>
 #include <vector>
@@ -22,6 +23,7 @@
 #include <atomic>
 
 #include "edgehip.h"
+#include "export_ring.h"
 
 namespace edgehip {
 
@@ -519,19 +521,9 @@ struct edgehip_ctx {
     edgehip_keyline *aos_host = nullptr;   // page-locked, same shape
     int32_t *aos_req_dev = nullptr, *aos_req_host = nullptr;   // [2][requests]: sequence ids | KeyLine counts (host side page-locked)
     int aos_requests = 0;
-    // edgehip_export_keylines / _fetch / _wait: the AoS KeyLine lists of output callbacks without a host synchronisation — packed
-    // in-stream behind the frame that finishes with the slot into a staging ring on the device, copied out on a stream of their own
-    struct KlExport {
-        static constexpr int R = 4;                 // tickets in flight (a group keeps at most three: two steps in flight + the one being delivered)
-        hipStream_t stream = nullptr;               // the copies to the host (never the log's stream: edgehip_read_nav_log synchronises that one)
-        edgehip_keyline *dev = nullptr;             // [R][n_cap][CAP]
-        int32_t *req = nullptr;                     // page-locked [R][n_cap]: sequence ids, read in place by the packing kernel
-        int n_cap = 0;
-        hipEvent_t ev_pack[R] = {}, ev_done[R] = {};
-        edgehip_keyline *host[R] = {};              // page-locked [n_cap][CAP] per ticket, allocated when a destination is not page-locked itself
-        struct Ticket { long long id = -1; int n = 0; bool fetched = false; std::vector<edgehip_keyline *> staged_dst; std::vector<int32_t> staged_kn; } t[R];
-        long long next = 0;
-    } *kl_export = nullptr;
+    // The lists of output callbacks without a host synchronisation, one staging ring (export_ring.h) per product:
+    edgehip::ExportRing kl_ring;    // edgehip_export_keylines / _fetch / _wait: [n_cap][CAP] AoS KeyLine records per entry, int32 sequence ids per row
+    edgehip::ExportRing ros_ring;   // edgehip_ros_export / _fetch / _wait: points | records per entry, k_prof | sequence ids per row (ros_edgemap.hip)
     edgehip_nav *nav_dev;  // [B] per-frame record
     edgehip_nav *nav_log;  // [nav_log_len][B] ring of per-frame records (optional)
     edgehip_nav_imu *nav_imu_log = nullptr;   // the IMU part of the same records, same ring (allocated when both the log and the IMU branch are on)
@@ -587,7 +579,8 @@ struct edgehip_ctx {
     // edgehip_net_enable: every sequence's edge map as 15-byte wire records (net_keyline) and their headers (net_keyline.hip); null when off
     struct NetStore;
     NetStore *net = nullptr;
-    // edgehip_ros_enable / edgehip_ros_export: the ROS nodelet's point cloud and EdgeMap records (ros_edgemap.hip); null when never used
+    // edgehip_ros_enable: the ROS nodelet's point cloud and EdgeMap records of the whole batch, and what ros_ring's entries have room for
+    // (ros_edgemap.hip); null when never used
     struct RosStore;
     RosStore *ros = nullptr;
 };
@@ -711,7 +704,44 @@ void net_free(edgehip_ctx *c);                      // net_keyline.hip: edgehip_
 // net_keyline.hip: the record store ([nseq][kl_size] records of 15 B, back to back) and its headers; false when off
 bool net_store(edgehip_ctx *c, const uint8_t **records, const edgehip_net_header **headers, int *kl_size);
 void surface_views_free(edgehip_ctx *c);            // surface_integrate.hip
-void ros_free(edgehip_ctx *c);                      // ros_edgemap.hip: the stores and the export ring, edgehip_destroy
-bool host_range_registered(const void *p, size_t bytes);  // api.hip: [p, p + bytes) lies inside a range page-locked by edgehip_register_host
+void ros_free(edgehip_ctx *c);                      // ros_edgemap.hip: the stores, edgehip_destroy
+
+// The B/C work enqueued on c->stream so far was the last reader of `slot`: a later stage A that detects into the slot waits for it
+// (only a stage-A stream of its own has to be told).
+inline int slot_read_done(edgehip_ctx *c, int slot) {
+    if (c->stream_a == c->stream) return 0;
+    EH_CHECK(hipEventRecord(c->ev_use[slot], c->stream));
+    c->use_valid[slot] = true;
+    return 0;
+}
+
+// A caller's [nseq] row of k_prof on its way to an in-stream kernel, through a page-locked row: the caller's array is free on return,
+// and nothing waits for the stream.
+struct KProfStage {
+    double *dev = nullptr, *host = nullptr;   // [nseq] device row, page-locked row
+    hipEvent_t ev = nullptr;                  // the last copy out of the page-locked row has finished
+    bool busy = false;
+    bool create(size_t nseq) {                // false: out of memory, nothing is left allocated
+        if (hipMalloc((void **)&dev, 8 * nseq) == hipSuccess && hipHostMalloc((void **)&host, 8 * nseq, hipHostMallocDefault) == hipSuccess &&
+            hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) return true;
+        (void)hipGetLastError();
+        destroy();
+        return false;
+    }
+    void destroy() {                          // (behind a synchronisation of the stream that push() used)
+        if (dev) (void)hipFree(dev);
+        if (host) (void)hipHostFree(host);
+        if (ev) (void)hipEventDestroy(ev);
+        *this = KProfStage();
+    }
+    int push(edgehip_ctx *c, const double *k_prof) {
+        if (busy) EH_CHECK(hipEventSynchronize(ev));   // (only for the copy of the push before this one)
+        memcpy(host, k_prof, 8 * (size_t)c->plan.nseq);
+        EH_CHECK(hipMemcpyAsync(dev, host, 8 * (size_t)c->plan.nseq, hipMemcpyHostToDevice, c->stream));
+        EH_CHECK(hipEventRecord(ev, c->stream));
+        busy = true;
+        return 0;
+    }
+};
 
 }  // namespace edgehip

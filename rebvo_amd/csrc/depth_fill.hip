@@ -446,11 +446,7 @@ int edgehip_depth_fill(edgehip_ctx *c, int slot) {
     hipLaunchKernelGGL(k_depth_fill<false>, dim3(c->plan.nseq), dim3(kDfThreads), lds, c->stream, a, d->lv);
     EH_LAUNCH_CHECK();
     d->filled = true;
-    if (c->stream_a != c->stream) {   // a later stage A that detects into this slot waits for the fill's reads
-        EH_CHECK(hipEventRecord(c->ev_use[slot], c->stream));
-        c->use_valid[slot] = true;
-    }
-    return 0;
+    return slot_read_done(c, slot);   // a later stage A that detects into this slot waits for the fill's reads
 }
 
 int edgehip_depth_fill_net(edgehip_ctx *c, float p_off_x, float p_off_y) {

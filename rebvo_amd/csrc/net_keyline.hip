@@ -9,14 +9,12 @@
 // The hot part is the store.  Records are 15 bytes and a sequence's records start at seq * kl_size * 15: aligned to nothing.  The
 // output is therefore cut by ADDRESS, not by record: a workgroup owns kNkWords consecutive 16-byte words of the store, computes every
 // record that touches them (16 records = 15 words; up to one record at either end is shared with the neighbour workgroup, which
-// computes it too) into LDS at the byte position it has in those words, and writes the words out as 16-byte nontemporal stores.  Only
-// the first and the last word of a sequence's count * 15 bytes can be partial; those are written byte by byte, so nothing outside the
-// sequence's own bytes is ever written and neighbouring sequences never touch the same byte.  The SoA reads are coalesced (KeyLine j
-// by lane j).
+// computes it too) into LDS at the byte position it has in those words, and flush_words (pack_flush.h) writes them out.  Only the
+// first and the last word of a sequence's count * 15 bytes can be partial.  The SoA reads are coalesced (KeyLine j by lane j).
 #include "ctx.h"
+#include "pack_flush.h"
 
 #include <cmath>
-#include <cstring>
 #include <vector>
 
 namespace edgehip {
@@ -103,17 +101,7 @@ __global__ __launch_bounds__(kNkThreads) void k_net_pack(NkArgs a) {
     }
     __syncthreads();
 
-    if (tid < kNkWords) {
-        const size_t g = w0 + (size_t)tid * 16;
-        if (g >= b0 && g + 16 <= b1) {
-            typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-            const u4v v = *reinterpret_cast<const u4v *>(buf + 16 + tid * 16);
-            __builtin_nontemporal_store(v, reinterpret_cast<u4v *>(a.rec + g));
-        } else if (g < b1 && g + 16 > b0) {   // the sequence's first or last word, partial
-            const int i0 = g < b0 ? (int)(b0 - g) : 0, i1 = g + 16 > b1 ? (int)(b1 - g) : 16;
-            for (int i = i0; i < i1; i++) a.rec[g + i] = buf[16 + tid * 16 + i];
-        }
-    }
+    flush_words<uint8_t, kNkThreads>(buf + 16, a.rec, w0, kNkWords, b0, b1);
 }
 
 }  // namespace edgehip
@@ -123,21 +111,17 @@ using namespace edgehip;
 struct edgehip_ctx::NetStore {
     int kl_size = 0;
     size_t rec_bytes = 0;              // nseq * kl_size * 15, rounded up to 16
-    void *arena = nullptr;             // records | headers | k_prof
+    void *arena = nullptr;             // records | headers
     uint8_t *rec = nullptr;
     edgehip_net_header *hdr = nullptr;
-    double *k_prof = nullptr;          // [nseq] device copy of edgehip_net_pack's argument
-    double *k_prof_host = nullptr;     // [nseq] page-locked staging of it
-    hipEvent_t ev_k = nullptr;         // the last copy out of the staging has finished
-    bool k_busy = false;
+    KProfStage k_prof;                 // edgehip_net_pack's argument on its way to the device
 };
 
 void edgehip::net_free(edgehip_ctx *c) {
     if (!c->net) return;
     (void)hipStreamSynchronize(c->stream);
     if (c->net->arena) (void)hipFree(c->net->arena);
-    if (c->net->k_prof_host) (void)hipHostFree(c->net->k_prof_host);
-    if (c->net->ev_k) (void)hipEventDestroy(c->net->ev_k);
+    c->net->k_prof.destroy();
     delete c->net;
     c->net = nullptr;
 }
@@ -155,35 +139,22 @@ int edgehip_net_enable(edgehip_ctx *c, int kl_size) {
     if (kl_size < 0 || kl_size > EDGEHIP_KEYLINE_MAX) { set_error("net_enable: kl_size must be in [0, EDGEHIP_KEYLINE_MAX]"); return EDGEHIP_ERR_ARG; }
     net_free(c);
     if (kl_size == 0) return 0;
-    auto *d = new edgehip_ctx::NetStore;
+    auto *d = c->net = new edgehip_ctx::NetStore;
     const size_t B = c->plan.nseq;
     d->kl_size = kl_size;
     d->rec_bytes = (B * (size_t)kl_size * 15 + 15) & ~(size_t)15;
-    const size_t bytes = d->rec_bytes + 16 * B + 8 * B;   // 16 B of room per header keeps the doubles behind them aligned
-    void *q = nullptr;
-    if (hipMalloc(&d->arena, bytes) != hipSuccess || hipHostMalloc(&q, 8 * B, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&d->ev_k, hipEventDisableTiming) != hipSuccess) {
+    const size_t bytes = d->rec_bytes + sizeof(edgehip_net_header) * B;
+    if (hipMalloc(&d->arena, bytes) != hipSuccess || !d->k_prof.create(B)) {
         (void)hipGetLastError();
-        if (d->arena) (void)hipFree(d->arena);
-        if (q) (void)hipHostFree(q);
-        delete d;
+        net_free(c);
         set_error("net_enable: allocation failed");
         return EDGEHIP_ERR_MEMORY;
     }
-    d->k_prof_host = (double *)q;
     d->rec = (uint8_t *)d->arena;
     d->hdr = (edgehip_net_header *)(d->rec + d->rec_bytes);
-    d->k_prof = (double *)(d->rec + d->rec_bytes + 16 * B);
-    if (hipMemsetAsync(d->arena, 0, bytes, c->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(d->arena);
-        (void)hipHostFree(d->k_prof_host);
-        (void)hipEventDestroy(d->ev_k);
-        delete d;
-        set_error("net_enable: hipMemsetAsync failed");
-        return EDGEHIP_ERR_DEVICE;
-    }
-    c->net = d;
+    const hipError_t z = hipMemsetAsync(d->arena, 0, bytes, c->stream);
+    if (z != hipSuccess) net_free(c);
+    EH_CHECK(z);
     return 0;
 }
 
@@ -201,18 +172,12 @@ int edgehip_net_pack(edgehip_ctx *c, int slot, int slot_pair, const double *k_pr
     if (int e = rot_materialize_enqueue(c, slot)) return e;
     if (pair) { if (int e = rot_materialize_enqueue(c, slot_pair)) return e; }
     if (int e = order_bc_after_a(c)) return e;
-    if (k_prof) {   // through the page-locked staging: the caller's array is free on return, and nothing waits for the stream
-        if (d->k_busy) EH_CHECK(hipEventSynchronize(d->ev_k));   // (only for the copy of the pack before this one)
-        memcpy(d->k_prof_host, k_prof, 8 * (size_t)c->plan.nseq);
-        EH_CHECK(hipMemcpyAsync(d->k_prof, d->k_prof_host, 8 * (size_t)c->plan.nseq, hipMemcpyHostToDevice, c->stream));
-        EH_CHECK(hipEventRecord(d->ev_k, c->stream));
-        d->k_busy = true;
-    }
+    if (k_prof) { if (int e = d->k_prof.push(c, k_prof)) return e; }
     NkArgs a;
     a.kls = kldev(c, slot);
     a.kls_pair = pair ? kldev(c, slot_pair) : nullptr;
     a.kns = c->kn_slot + (size_t)slot * c->plan.nseq;
-    a.k_prof = k_prof ? d->k_prof : nullptr;
+    a.k_prof = k_prof ? d->k_prof.dev : nullptr;
     a.seqs = c->seq;
     a.rec = d->rec;
     a.hdr = d->hdr;
@@ -222,11 +187,9 @@ int edgehip_net_pack(edgehip_ctx *c, int slot, int slot_pair, const double *k_pr
     const unsigned nblk = (unsigned)(((size_t)std::min(d->kl_size, c->plan.cap) * 15 + 15 + kNkBytes - 1) / kNkBytes);
     hipLaunchKernelGGL(k_net_pack, dim3(std::max(nblk, 1u), c->plan.nseq), dim3(kNkThreads), 0, c->stream, a);
     EH_LAUNCH_CHECK();
-    if (c->stream_a != c->stream) {   // a later stage A that detects into these slots waits for the pack's reads
-        EH_CHECK(hipEventRecord(c->ev_use[slot], c->stream));
-        c->use_valid[slot] = true;
-        if (pair) { EH_CHECK(hipEventRecord(c->ev_use[slot_pair], c->stream)); c->use_valid[slot_pair] = true; }
-    }
+    // a later stage A that detects into these slots waits for the pack's reads
+    if (int e = slot_read_done(c, slot)) return e;
+    if (pair) { if (int e = slot_read_done(c, slot_pair)) return e; }
     return 0;
 }
 

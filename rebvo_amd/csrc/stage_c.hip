@@ -1891,19 +1891,9 @@ static int frame_enqueue(edgehip_ctx *c, int sn, int so, int sp, int have_pair, 
         EH_TRY(glue(c, 3, sn, have_pair));                                                       // :550-606
     }
 #undef EH_TRY
-    // B/C of this frame were the last readers of both slots (only a stage-A stream of its own has to be told)
-    if (c->stream_a != c->stream) {
-        EH_CHECK(hipEventRecord(c->ev_use[sn], c->stream));
-        c->use_valid[sn] = true;
-        if (so >= 0) {
-            EH_CHECK(hipEventRecord(c->ev_use[so], c->stream));
-            c->use_valid[so] = true;
-        }
-        if (sp >= 0) {
-            EH_CHECK(hipEventRecord(c->ev_use[sp], c->stream));
-            c->use_valid[sp] = true;
-        }
-    }
+    // B/C of this frame were the last readers of its slots
+    for (int s : {sn, so, sp})
+        if (s >= 0) { if (int e = slot_read_done(c, s)) return e; }
     return 0;
 }
 

@@ -247,7 +247,18 @@ def test_in_stream_keyline_export_equals_the_synchronising_download_with_frames_
     for h in held:
         eh.export_drop(h)
     eh.export_drop(eh.export_keylines(seqs))
-    fresh = edgehip.EdgeHip(p, nseq=2, nslots=3, device=0)
+    # a ticket released unfetched frees its entry only behind its pack (the kernel reads the entry's request row in place): exports of
+    # OTHER sequence lists, of other lengths, into the same entries are right
+    held = [eh.export_keylines(seqs) for _ in range(4)]
+    for h in held:
+        eh.export_drop(h)
+    old = (ref.cur_slot() + 2) % 3
+    for other in ([1, 2, 0], [2, 1], [0], [1, 3, 2]):
+        lists = [ref.download_keylines(s_, old, want_mask=False)[0] for s_ in other]
+        out = eh.export_wait(eh.export_fetch(eh.export_keylines(other), [len(x) for x in lists], registered=False))
+        for a, b in zip(out, lists):
+            assert len(a) == len(b) > 1000 and a.tobytes() == b.tobytes(), other
+    fresh =edgehip.EdgeHip(p, nseq=2, nslots=3, device=0)
     assert fresh.lib.edgehip_export_keylines(fresh.ctx, 1, arr.ctypes.data_as(C.c_void_p), C.byref(t)) != 0      # no frame pair yet
     for e in (eh, ref, fresh):
         e.close()
