@@ -298,6 +298,15 @@ int edgehip_rotate_keylines(edgehip_ctx *ctx, int slot, const double *R /* [nseq
 /* edge_tracker::directed_matching (rebvo_second_t.cpp:410; edge_tracker.cpp:302-374, 158-295) with
  * V, P_V, R taken from seq_state; the match count lands in seq_state.klm_num / kf_matchs. */
 int edgehip_directed_matching(edgehip_ctx *ctx, int slot_new, int slot_old);
+/* TEST SUPPORT ONLY, not part of the product surface: the matching of a frame that matches in one pass (no stereo pair, no IMU
+ * branch), on uploaded lists.  Enqueues exactly what edgehip_process_frame enqueues there: FordwardMatch's arbitration keys of slot_old
+ * (the keys the tracker's last evaluation posts in a frame), rotate_keylines(exp(seq_state.W)) out of place together with the
+ * arbitration (seq_state.R receives the back-rotation, :360-361), then directed_matching with FordwardMatch's copy inside, with V, P_V
+ * from seq_state.  fill != 0: the ten matching fields of slot_new are taken as unwritten (a detector that left them to this call) and
+ * every KeyLine gets them: the match's, the forward match's, or a fresh KeyLine's (edge_finder.cpp:176-196).  Counts land in
+ * seq_state.klm_fwd / klm_num / kf_matchs (added to what is there).  slot_old keeps its turned values beside its arrays until the next
+ * stage-level call or download reads it.  EDGEHIP_ERR_STATE in a context that does not match in one pass (stereo_available). */
+int edgehip_match_one_pass(edgehip_ctx *ctx, int slot_new, int slot_old, int fill);
 /* Regularize_1_iter + UpdateInverseDepthKalman fused (rebvo_second_t.cpp:453, 460;
  * edge_tracker.cpp:87-148, 695-724, 954-1055).  do_regularize/do_ekf select either half (tests). */
 int edgehip_regularize_ekf(edgehip_ctx *ctx, int slot, int do_regularize, int do_ekf);

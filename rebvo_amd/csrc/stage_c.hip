@@ -1578,6 +1578,28 @@ int edgehip_directed_matching(edgehip_ctx *c, int slot_new, int slot_old) {
     if (int e = chk2(c, slot_new, slot_old)) return e;
     return directed_enqueue(c, slot_new, slot_old);
 }
+// Test support only: what frame_enqueue enqueues for a frame that matches in one pass, on uploaded lists.  The keys come from
+// k_fwd_key (in a frame the minimiser's last evaluation posts the same values), the rest are the frame's own two calls; no kernel
+// of its own.  k_rotate<OUT, WIN> forms R0 = exp(W) from each sequence's state and stores the back-rotation in state.R.
+int edgehip_match_one_pass(edgehip_ctx *c, int slot_new, int slot_old, int fill) {
+    EH_ENTER(c);
+    if (int e = chk2(c, slot_new, slot_old)) return e;
+    if (slot_new == slot_old) { set_error("match_one_pass: one slot for both lists"); return EDGEHIP_ERR_ARG; }
+    if (!frame_matches_in_one_pass(c, -1)) { set_error("match_one_pass: this context does not match in one pass"); return EDGEHIP_ERR_STATE; }
+    const DevicePlan &pl = c->plan;
+    const size_t B = pl.nseq;
+    EH_CHECK(hipMemsetAsync(c->fwd_key, 0, sizeof(unsigned long long) * B * pl.cap, c->stream));
+    c->fwd_cleared = false;   // fwd_win is reset by forward_rotate_one_pass_enqueue
+    {
+        ProfScope ps(c, PROF_C_FORWARD);
+        hipLaunchKernelGGL(k_fwd_key, dim3((pl.cap + 255) / 256, 1, pl.nseq), dim3(256), 0, c->stream, kldev(c, slot_old),
+                           c->kn_slot + slot_old * B, c->kn_slot + slot_new * B, c->fwd_key, pl.cap);
+        EH_LAUNCH_CHECK();
+    }
+    if (int e = forward_rotate_one_pass_enqueue(c, slot_old, slot_new)) return e;
+    c->fwd_fill[slot_new] = fill != 0;
+    return directed_enqueue(c, slot_new, slot_old, true);
+}
 int edgehip_regularize_ekf(edgehip_ctx *c, int slot, int do_reg, int do_ekf) {
     EH_ENTER(c);
     if (int e = chk2(c, slot, slot)) return e;

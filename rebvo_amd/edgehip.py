@@ -250,6 +250,7 @@ EXPORTS = [
     "edgehip_net_keylines_device", "edgehip_upload_net_keylines", "edgehip_depth_fill_net",
     "edgehip_ros_enable", "edgehip_ros_pack", "edgehip_download_ros_edgemap", "edgehip_download_ros_edgemaps_batch",
     "edgehip_ros_edgemap_device", "edgehip_ros_edgemap_from_device", "edgehip_ros_export", "edgehip_ros_export_fetch", "edgehip_ros_export_wait",
+    "edgehip_match_one_pass",
 ]
 
 _lib = None
@@ -545,6 +546,10 @@ class EdgeHip:
 
     def directed_matching(self, slot_new, slot_old):
         self._ck(self.lib.edgehip_directed_matching(self.ctx, slot_new, slot_old))
+
+    def match_one_pass(self, slot_new, slot_old, fill=False):
+        """edgehip_match_one_pass (test support only): the one-pass matching of a whole frame on uploaded lists; R0 = exp(state.W)."""
+        self._ck(self.lib.edgehip_match_one_pass(self.ctx, slot_new, slot_old, int(bool(fill))))
 
     def regularize_ekf(self, slot, do_regularize=True, do_ekf=True):
         self._ck(self.lib.edgehip_regularize_ekf(self.ctx, slot, int(do_regularize), int(do_ekf)))
