@@ -783,6 +783,65 @@ int edgehip_ros_export_fetch(edgehip_ctx *ctx, int ticket, const int32_t *kn, ed
                              edgehip_ros_keyline *const *keylines_dst);
 int edgehip_ros_export_wait(edgehip_ctx *ctx, int ticket);
 
+/* ---- key-frame tracking (TrackKeyFrames) ------------------------------------------------------------------------------------
+ * What SecondThread does with REBVO/TrackKeyFrames = 1 (rebvo_second_t.cpp:156-162, 429-444, 587-598): it keeps a current key frame —
+ * a copy of an edge map with its pose (keyframe.cpp:28-43) — and, after every frame pair whose matching succeeded, repairs the matches
+ * between that key frame and the newest edge map in both directions with kfvo::buildForwardMatch, forwardCorrectAugmentate and
+ * correctAugmentate (src/mtracklib/kfvo.cpp:739-771, 969-1142, 804-966); a new key frame is taken when the repaired back-match count drops
+ * below min(TrackPoints, KNum) * KFSavePercent.  Here every sequence has ONE key frame in HBM, the reference's kf_list.back(); older key
+ * frames are the caller's to take when `inserted` is set.  Only m_id_f of the key frame, m_id_kf of the frame lists and the counts
+ * change: nothing feeds back into the odometry.  Every id and count equals the reference's (integers; the distances behind them are fp64
+ * in the reference's order of operations; tests/keyframe_track_port.py restates the rule).
+ * Preconditions: every p_m finite; m_id, m_id_f, m_id_kf negative or in range of the list they index.  Out-of-range links end a chain;
+ * every chain walk is capped at the length of the list it walks (on finite p_m it ends before), a capped walk sets `guard`.
+ * Not for a context with the device IMU branch (EDGEHIP_ERR_STATE). */
+/* keyframe's pose block (keyframe.h: t, K, Rot, RotLie, Vel, Pose, PoseLie, Pos). */
+typedef struct edgehip_kf_pose {
+    double t, K;
+    double Rot[9], RotLie[3], Vel[3], Pose[9], PoseLie[3], Pos[3];
+} edgehip_kf_pose;
+/* Per-frame record of the key-frame tracking, beside edgehip_nav (read by edgehip_read_keyframe_track). */
+typedef struct edgehip_kf_track {
+    int32_t fow_m0, fow_m;     /* num_kf_fow_m after buildForwardMatch / after forwardCorrectAugmentate (0 when the steps did not run) */
+    int32_t back_m0, back_m;   /* num_kf_back_m as directed_matching left it / after correctAugmentate (equal when the steps did not run) */
+    int32_t inserted;          /* this frame took a new key frame (either rule) */
+    int32_t kf_count;          /* kf_list.size() */
+    int32_t guard;             /* != 0: a chain walk hit its cap (bit 0) or met a match outside its list (bit 1): a precondition was broken */
+    int32_t kf_kn;             /* KeyLines of the current key frame */
+} edgehip_kf_track;
+/* enable = 1: allocates every sequence's key frame (all KeyLine fields, about 140 B per KeyLine of capacity) and the scratch of the
+ * repair (20 B per KeyLine), empty (kf_count = 0), and switches the feature on inside edgehip_process_frame — the first-key-frame rule on
+ * the old slot before a frame pair is processed (:156-162), the three steps behind directed_matching for sequences with klm_num >=
+ * MatchThreshold with (dist_thesh, dist_tolerance, augmentate) = (10, 0, true) (:429-444), the insertion from the new slot at the frame's
+ * end when save_keyframes != 0 and the criterion holds (:591-596); edgehip_nav::kf_matchs / edgehip_seq_state::kf_matchs then carry the
+ * repaired back count, as num_kf_back_m does upstream.  kf_save_percent = REBVO/KFSavePercent, save_keyframes = REBVO::saveKeyframes.
+ * enable = 2: the same store for the entry points below alone; edgehip_process_frame leaves the key frames to the caller.
+ * enable = 0 frees everything (the default state: edgehip_process_frame enqueues exactly what it does without the feature). */
+int edgehip_keyframe_track_enable(edgehip_ctx *ctx, int enable, double kf_save_percent, int save_keyframes);
+/* keyframe(...) + kfvo::resetForwardMatch + kfvo::resetKFMatch (kfvo.cpp:774-787) from ring slot `slot` for the sequences with mask[seq]
+ * != 0 (mask == NULL: all): the key frame becomes a copy of the slot's KeyLines with m_id_f = i, rho0 = rho, s_rho0 = s_rho, and the
+ * slot's m_id_kf = i; kf_count goes up by one.  pose[nseq] (entries of unmasked sequences are ignored), or NULL for the newest nav
+ * record's t, Rot, RotLie, Vel, Pose, PoseLie, Pos and edgehip_seq_state::K.  In-stream, no synchronisation. */
+int edgehip_keyframe_insert(edgehip_ctx *ctx, int slot, const uint8_t *mask, const edgehip_kf_pose *pose);
+/* kfvo::buildForwardMatch(kf, new, old): the key frame's m_id_f, which index the list slot_new's KeyLines were matched against (their
+ * m_id), re-pointed into slot_new.  counts[nseq] (may be NULL: no synchronisation) = the function's return value. */
+int edgehip_keyframe_build_forward_match(edgehip_ctx *ctx, int slot_new, int32_t *counts);
+/* kfvo::forwardCorrectAugmentate / kfvo::correctAugmentate(kf, new, Pose, Pos, dist_thresh, dist_tolerance, augmentate) for every
+ * sequence: Pose[nseq][9], Pos[nseq][3], or both NULL for Pose * R and Pos - Pose * R * V * K from edgehip_seq_state (what the frame
+ * driver has at that point, rebvo_second_t.cpp:435-436).  counts as above. */
+int edgehip_keyframe_forward_correct(edgehip_ctx *ctx, int slot_new, const double *Pose, const double *Pos, double dist_thresh,
+                                     double dist_tolerance, int augmentate, int32_t *counts);
+int edgehip_keyframe_back_correct(edgehip_ctx *ctx, int slot_new, const double *Pose, const double *Pos, double dist_thresh,
+                                  double dist_tolerance, int augmentate, int32_t *counts);
+/* The records of the last processed frame (the stage-level entry points above write their counts into the same fields).  out[nseq].
+ * Synchronises. */
+int edgehip_read_keyframe_track(edgehip_ctx *ctx, edgehip_kf_track *out);
+/* The current key frame of sequence `seq`: kl has room for max_points records (may be NULL), pose and kf_count may be NULL.
+ * Synchronises. */
+int edgehip_download_keyframe(edgehip_ctx *ctx, int seq, edgehip_keyline *kl, int32_t *kn_out, edgehip_kf_pose *pose, int32_t *kf_count);
+/* Replace it (kf_count goes up by one; the records are taken as they are, no reset).  Synchronises. */
+int edgehip_upload_keyframe(edgehip_ctx *ctx, int seq, const edgehip_keyline *kl, int32_t kn, const edgehip_kf_pose *pose);
+
 /* ---- measurement ------------------------------------------------------------------------------------- */
 /* Names of the kernel groups timed by the built-in HIP-event profiler, and their accumulated device time.
  * edgehip_profile_enable(ctx, 1) brackets every launch group with events on the context stream (adds host

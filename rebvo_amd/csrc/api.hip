@@ -649,6 +649,7 @@ int edgehip_destroy(edgehip_ctx *c) {
     depth_fill_free(c);
     net_free(c);
     ros_free(c);
+    kf_track_free(c);
     CtxAllocs *mine = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_allocs_mu);
@@ -716,6 +717,7 @@ int edgehip_reset(edgehip_ctx *c) {
     EH_CHECK(hipMemsetAsync(c->framecount, 0, sizeof(uint32_t) * c->fc_rows * B, c->stream));
     EH_CHECK(hipMemsetAsync(c->kn_slot, 0, sizeof(int32_t) * S * B, c->stream));
     if (c->imu_enabled) { if (int e = imu_reset_enqueue(c)) return e; }
+    if (int e = kf_track_reset_enqueue(c)) return e;
     EH_CHECK(hipStreamSynchronize(c->stream));
     c->frame_slot = -1;
     c->frames_seen = 0;

@@ -583,6 +583,9 @@ struct edgehip_ctx {
     // (ros_edgemap.hip); null when never used
     struct RosStore;
     RosStore *ros = nullptr;
+    // edgehip_keyframe_track_enable: every sequence's current key frame and the scratch of the match repair (keyframe_track.hip); null when off
+    struct KfTrack;
+    KfTrack *kftrack = nullptr;
 };
 
 namespace edgehip {
@@ -705,6 +708,13 @@ void net_free(edgehip_ctx *c);                      // net_keyline.hip: edgehip_
 bool net_store(edgehip_ctx *c, const uint8_t **records, const edgehip_net_header **headers, int *kl_size);
 void surface_views_free(edgehip_ctx *c);            // surface_integrate.hip
 void ros_free(edgehip_ctx *c);                      // ros_edgemap.hip: the stores, edgehip_destroy
+void kf_track_free(edgehip_ctx *c);                 // keyframe_track.hip: edgehip_keyframe_track_enable(ctx, 0, ...), edgehip_destroy
+int kf_track_reset_enqueue(edgehip_ctx *c);         // edgehip_reset: no key frame, empty records (no-op when off)
+// keyframe_track.hip, the frame driver's hooks (only with c->kftrack): the first-key-frame rule on the old slot at the frame's begin
+// (rebvo_second_t.cpp:156-162), the three repair steps behind directed_matching (:429-444), the insertion rule at the frame's end (:591-596)
+int kf_frame_begin_enqueue(edgehip_ctx *c, int slot_old);
+int kf_frame_track_enqueue(edgehip_ctx *c, int slot_new);
+int kf_frame_end_enqueue(edgehip_ctx *c, int slot_new);
 
 // The B/C work enqueued on c->stream so far was the last reader of `slot`: a later stage A that detects into the slot waits for it
 // (only a stage-A stream of its own has to be told).

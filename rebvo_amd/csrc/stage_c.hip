@@ -1877,6 +1877,7 @@ static int frame_enqueue(edgehip_ctx *c, int sn, int so, int sp, int have_pair, 
         }
         EH_TRY(imu_post_enqueue(c, sn, have_pair));                                                  // :280-312, :519-606
     } else if (have_pair) {
+        if (c->kftrack) EH_TRY(kf_frame_begin_enqueue(c, so));                                    // rebvo_second_t.cpp:156-162 (TrackKeyFrames)
         EH_TRY(quantile_enqueue(c, so, kRhoMin, kRhoMax, c->p.qcut_quantile, c->p.qcut_nbins, true, retune_in_quantile ? sn : -1));  // rebvo_second_t.cpp:145-168, :172
         EH_TRY(build_field_enqueue(c, sn, c->p.search_range, -1.f, c->fwd_mode != 1));            // :177
         c->fwd_key_in_tvr = c->fwd_mode != 1;
@@ -1898,6 +1899,7 @@ static int frame_enqueue(edgehip_ctx *c, int sn, int so, int sp, int have_pair, 
         }
         if (c->fwd_mode == 2) { ProfScope ps(c, PROF_C_POSE); EH_TRY(glue(c, 1, sn, have_pair)); }   // :387-397
         EH_TRY(directed_enqueue(c, sn, so, one_pass));                                           // :410
+        if (c->kftrack) EH_TRY(kf_frame_track_enqueue(c, sn));                                   // :429-444 (its own :412 predicate per sequence)
         EH_TRY(regekf_enqueue(c, sn, 1, 1, true));                                               // :412-422 (in k_regularize), :453, :460
         if (sp >= 0) {                                                                           // :465-486
             EH_TRY(stereo_enqueue(c, sn, sp, c->rig.t, c->rig.R, c->p.match_thresh_module, c->p.match_thresh_angle, c->rig.max_radius,
@@ -1912,6 +1914,7 @@ static int frame_enqueue(edgehip_ctx *c, int sn, int so, int sp, int have_pair, 
         ProfScope ps(c, PROF_C_POSE);
         EH_TRY(glue(c, 3, sn, have_pair));                                                       // :550-606
     }
+    if (c->kftrack && have_pair && !c->imu_enabled) EH_TRY(kf_frame_end_enqueue(c, sn));         // :591-596
 #undef EH_TRY
     // B/C of this frame were the last readers of its slots
     for (int s : {sn, so, sp})

@@ -461,6 +461,7 @@ int edgehip_imu_enable(edgehip_ctx *c, const edgehip_imu_params *imu) {
     if (c->frames_seen != 0) { set_error("edgehip_imu_enable: call before the first frame"); return EDGEHIP_ERR_STATE; }
     if (c->tracker_f32) { set_error("edgehip_imu_enable: the float tracker is Minimizer_RV<float> (ImuMode 0): edgehip_set_tracker_precision(ctx, 64) first"); return EDGEHIP_ERR_STATE; }
     if (c->rig.enabled) { set_error("edgehip_imu_enable: the device IMU branch does not run the stereo rig (use the stage entry points)"); return EDGEHIP_ERR_STATE; }
+    if (c->kftrack) { set_error("edgehip_imu_enable: the device IMU branch does not track key frames (edgehip_keyframe_track_enable(ctx, 0, ...) first)"); return EDGEHIP_ERR_STATE; }
     const size_t B = c->plan.nseq;
     if (!c->imu_pinned_ok) {
         // All or nothing: a call that fails half-way leaves the context without IMU buffers, so that a second call starts over

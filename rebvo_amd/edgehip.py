@@ -220,6 +220,20 @@ class SurfaceViewsParams(C.Structure):
     _fields_ = [("capacity", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32)]
 
 
+class KfPose(C.Structure):
+    """edgehip_kf_pose: a key frame's pose block (t, K, Rot, RotLie, Vel, Pose, PoseLie, Pos)."""
+    _fields_ = [("t", C.c_double), ("K", C.c_double), ("Rot", C.c_double * 9), ("RotLie", C.c_double * 3), ("Vel", C.c_double * 3),
+                ("Pose", C.c_double * 9), ("PoseLie", C.c_double * 3), ("Pos", C.c_double * 3)]
+
+
+class KfTrack(C.Structure):
+    """edgehip_kf_track: the per-frame record of the key-frame tracking."""
+    _fields_ = [("fow_m0", C.c_int32), ("fow_m", C.c_int32), ("back_m0", C.c_int32), ("back_m", C.c_int32),
+                ("inserted", C.c_int32), ("kf_count", C.c_int32), ("guard", C.c_int32), ("kf_kn", C.c_int32)]
+
+
+KF_POSE_DTYPE = np.dtype(KfPose)
+KF_TRACK_DTYPE = np.dtype(KfTrack)
 NAV_DTYPE = np.dtype(Nav)   # numpy view of edgehip_nav (same offsets as the ctypes struct)
 assert NAV_DTYPE.itemsize == C.sizeof(Nav)
 
@@ -251,6 +265,8 @@ EXPORTS = [
     "edgehip_ros_enable", "edgehip_ros_pack", "edgehip_download_ros_edgemap", "edgehip_download_ros_edgemaps_batch",
     "edgehip_ros_edgemap_device", "edgehip_ros_edgemap_from_device", "edgehip_ros_export", "edgehip_ros_export_fetch", "edgehip_ros_export_wait",
     "edgehip_match_one_pass",
+    "edgehip_keyframe_track_enable", "edgehip_keyframe_insert", "edgehip_keyframe_build_forward_match", "edgehip_keyframe_forward_correct",
+    "edgehip_keyframe_back_correct", "edgehip_read_keyframe_track", "edgehip_download_keyframe", "edgehip_upload_keyframe",
 ]
 
 _lib = None
@@ -1016,6 +1032,74 @@ class EdgeHip:
         self._ck(self.lib.edgehip_upload_keylines(self.ctx, seq, slot, kl.ctypes.data_as(C.c_void_p), len(kl),
                                                   None if m is None else m.ctypes.data_as(C.c_void_p),
                                                   C.c_float(retuned)))
+
+    # ---- key-frame tracking (TrackKeyFrames) ----
+    def keyframe_track_enable(self, enable=True, kf_save_percent=0.7, save_keyframes=True, in_frame_driver=True):
+        """KFSavePercent and REBVO::saveKeyframes; enable=False frees the key frames and takes the steps out of process_frame;
+        in_frame_driver=False keeps the store for the stage-level calls below and leaves process_frame as it is without the feature."""
+        mode = 0 if not enable else (1 if in_frame_driver else 2)
+        self._ck(self.lib.edgehip_keyframe_track_enable(self.ctx, mode, C.c_double(kf_save_percent), int(bool(save_keyframes))))
+
+    @staticmethod
+    def kf_pose(Pose=None, Pos=None, t=0.0, K=1.0):
+        """A KfPose with the given pose (the other blocks zero: the tracking reads only Pose and Pos)."""
+        q = KfPose()
+        q.t, q.K = t, K
+        q.Pose[:] = list(np.asarray(np.eye(3) if Pose is None else Pose, np.float64).reshape(9))
+        q.Pos[:] = list(np.asarray(np.zeros(3) if Pos is None else Pos, np.float64).reshape(3))
+        return q
+
+    def keyframe_insert(self, slot, mask=None, poses=None):
+        """keyframe(...) + resetForwardMatch + resetKFMatch from `slot` for the masked sequences (None: all); poses: one KfPose per
+        sequence, or None for the newest nav record and seq_state.K."""
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(bool), np.uint8)
+        assert m is None or m.shape == (self.nseq,)
+        arr = None if poses is None else (KfPose * self.nseq)(*poses)
+        self._ck(self.lib.edgehip_keyframe_insert(self.ctx, slot, None if m is None else m.ctypes.data_as(C.c_void_p), arr))
+
+    def _kf_pose_args(self, Pose, Pos):
+        if Pose is None and Pos is None:
+            return None, None, None
+        P = np.ascontiguousarray(np.broadcast_to(np.asarray(Pose, np.float64).reshape(-1, 9), (self.nseq, 9)))
+        T = np.ascontiguousarray(np.broadcast_to(np.asarray(Pos, np.float64).reshape(-1, 3), (self.nseq, 3)))
+        return _dp(P), _dp(T), (P, T)
+
+    def keyframe_build_forward_match(self, slot_new):
+        cnt = np.zeros(self.nseq, np.int32)
+        self._ck(self.lib.edgehip_keyframe_build_forward_match(self.ctx, slot_new, cnt.ctypes.data_as(C.c_void_p)))
+        return cnt
+
+    def keyframe_forward_correct(self, slot_new, Pose=None, Pos=None, dist_thresh=10.0, dist_tolerance=0.0, augmentate=True):
+        """Pose [nseq][3][3], Pos [nseq][3] (both None: Pose*R, Pos - Pose*R*V*K from seq_state) -> counts[nseq]."""
+        cnt = np.zeros(self.nseq, np.int32)
+        pp, pt, keep = self._kf_pose_args(Pose, Pos)
+        self._ck(self.lib.edgehip_keyframe_forward_correct(self.ctx, slot_new, pp, pt, C.c_double(dist_thresh), C.c_double(dist_tolerance),
+                                                           int(bool(augmentate)), cnt.ctypes.data_as(C.c_void_p)))
+        return cnt
+
+    def keyframe_back_correct(self, slot_new, Pose=None, Pos=None, dist_thresh=10.0, dist_tolerance=0.0, augmentate=True):
+        cnt = np.zeros(self.nseq, np.int32)
+        pp, pt, keep = self._kf_pose_args(Pose, Pos)
+        self._ck(self.lib.edgehip_keyframe_back_correct(self.ctx, slot_new, pp, pt, C.c_double(dist_thresh), C.c_double(dist_tolerance),
+                                                        int(bool(augmentate)), cnt.ctypes.data_as(C.c_void_p)))
+        return cnt
+
+    def read_keyframe_track(self):
+        """The per-frame records as a structured array [nseq] (KF_TRACK_DTYPE)."""
+        out = np.zeros(self.nseq, KF_TRACK_DTYPE)
+        self._ck(self.lib.edgehip_read_keyframe_track(self.ctx, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def download_keyframe(self, seq):
+        """-> (KeyLine records [kn], KfPose, kf_count) of the sequence's current key frame."""
+        kl = np.zeros(self.cap, KEYLINE_DTYPE)
+        kn, cnt, pose = C.c_int32(0), C.c_int32(0), KfPose()
+        self._ck(self.lib.edgehip_download_keyframe(self.ctx, seq, kl.ctypes.data_as(C.c_void_p), C.byref(kn), C.byref(pose), C.byref(cnt)))
+        return kl[:kn.value].copy(), pose, cnt.value
+
+    def upload_keyframe(self, seq, kl, pose):
+        kl = np.ascontiguousarray(kl, dtype=KEYLINE_DTYPE)
+        self._ck(self.lib.edgehip_upload_keyframe(self.ctx, seq, kl.ctypes.data_as(C.c_void_p), len(kl), C.byref(pose)))
 
     def download_plane(self, seq, which):
         idx = {"img0": 0, "img1": 1, "dog": 2, "dx": 3, "dy": 4}[which]
