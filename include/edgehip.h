@@ -789,8 +789,8 @@ int edgehip_ros_export_wait(edgehip_ctx *ctx, int ticket);
  * between that key frame and the newest edge map in both directions with kfvo::buildForwardMatch, forwardCorrectAugmentate and
  * correctAugmentate (src/mtracklib/kfvo.cpp:739-771, 969-1142, 804-966); a new key frame is taken when the repaired back-match count drops
  * below min(TrackPoints, KNum) * KFSavePercent.  Here every sequence has ONE key frame in HBM, the reference's kf_list.back(); older key
- * frames are the caller's to take when `inserted` is set.  Only m_id_f of the key frame, m_id_kf of the frame lists and the counts
- * change: nothing feeds back into the odometry.  Every id and count equals the reference's (integers; the distances behind them are fp64
+ * frames go into the key-frame list below when it is enabled, and are otherwise the caller's to take when `inserted` is set.  Only
+ * m_id_f of the key frame, m_id_kf of the frame lists and the counts change: nothing feeds back into the odometry.  Every id and count equals the reference's (integers; the distances behind them are fp64
  * in the reference's order of operations; tests/keyframe_track_port.py restates the rule).
  * Preconditions: every p_m finite; m_id, m_id_f, m_id_kf negative or in range of the list they index.  Out-of-range links end a chain;
  * every chain walk is capped at the length of the list it walks (on finite p_m it ends before), a capped walk sets `guard`.
@@ -841,6 +841,48 @@ int edgehip_read_keyframe_track(edgehip_ctx *ctx, edgehip_kf_track *out);
 int edgehip_download_keyframe(edgehip_ctx *ctx, int seq, edgehip_keyline *kl, int32_t *kn_out, edgehip_kf_pose *pose, int32_t *kf_count);
 /* Replace it (kf_count goes up by one; the records are taken as they are, no reset).  Synchronises. */
 int edgehip_upload_keyframe(edgehip_ctx *ctx, int seq, const edgehip_keyline *kl, int32_t kn, const edgehip_kf_pose *pose);
+/* REBVO::saveKeyframes at run time: the criterion of :591-596 inserts only while the flag is set (the first-key-frame rule does not ask
+ * it).  Takes effect from the next enqueued frame; the key frames and the list below stay as they are (edgehip_keyframe_track_enable
+ * sets the flag too, but frees both).  EDGEHIP_ERR_STATE without key-frame tracking. */
+int edgehip_keyframe_set_save(edgehip_ctx *ctx, int save_keyframes);
+
+/* ---- the key-frame list (REBVO::kf_list) -------------------------------------------------------------------------------------
+ * Every key frame a sequence replaces — through the frame driver's two rules, edgehip_keyframe_insert or edgehip_upload_keyframe —
+ * is kept on the device as it was at that moment: its pose block and its KeyLines as the 168-byte records edgehip_download_keyframe
+ * would have returned (score 0, net_id -1, bytes 36..39 zero, the stereo triple (-1, 1.0, 20.0) unless the context keeps it), which
+ * are the records keyframe::dumpToBinaryFile writes.  The key frames of a sequence are numbered from 0 in the order it took them
+ * (the ordinal); the current one is kf_count - 1 and is NOT in the list, it retires when the next one replaces it.  Retiring is
+ * in-stream, inside the captured frame, with no synchronisation; a frame that replaces nothing pays one launch of empty workgroups.
+ * Each sequence has a ring of `capacity` entries: ordinal j lives in position j % capacity, and a retirement into a full ring
+ * overwrites the oldest entry (first moves up, overwritten counts it).
+ * Memory: (168 B x max_points, rounded up to 16) x capacity x nseq for the records — 2.75 GB per unit of capacity at 1024 sequences of
+ * 16000 KeyLines — and 264 B x capacity x nseq for the headers. */
+typedef struct edgehip_kf_list_info {
+    int32_t kf_count;      /* key frames taken so far (edgehip_kf_track::kf_count) */
+    int32_t first, held;   /* the list holds the ordinals [first, first + held); first + held == kf_count - 1 once a key frame exists */
+    int32_t overwritten;   /* entries the ring has dropped since the list was enabled or reset */
+} edgehip_kf_list_info;
+/* Allocates the rings, empty (a sequence that has key frames already starts its list at the current one's ordinal).  capacity == 0
+ * frees the list alone; edgehip_keyframe_track_enable (any mode) frees it with the key frames; edgehip_reset empties it.
+ * EDGEHIP_ERR_STATE without key-frame tracking (capacity > 0), EDGEHIP_ERR_MEMORY when the allocation fails: the list is then off and
+ * the context stays usable. */
+int edgehip_keyframe_list_enable(edgehip_ctx *ctx, int capacity);
+/* info[nseq].  Synchronises. */
+int edgehip_keyframe_list_info(edgehip_ctx *ctx, edgehip_kf_list_info *info);
+/* Entry `ordinal` of sequence `seq`: kl has room for max_points records (may be NULL), of which *kn_out are copied — a straight copy,
+ * the list holds them as records; pose may be NULL.  EDGEHIP_ERR_ARG for an ordinal the list does not hold (overwritten, current, or
+ * future); nothing is written then.  Synchronises. */
+int edgehip_download_keyframe_list(edgehip_ctx *ctx, int seq, int ordinal, edgehip_keyline *kl, int32_t *kn_out, edgehip_kf_pose *pose);
+/* The same for n requests (seqs[j], ordinals[j]) -> kl[j] (array or entries may be NULL), kn_out[j], pose[j] (arrays may be NULL).
+ * Two synchronisations however many requests: one for the headers, which say how many records to copy, one for the records. */
+int edgehip_download_keyframe_list_batch(edgehip_ctx *ctx, int n, const int32_t *seqs, const int32_t *ordinals, edgehip_keyline *const *kl,
+                                         int32_t *kn_out, edgehip_kf_pose *pose);
+/* List entry ordinals[seq] of every sequence back into ring slot `slot` as KeyLines (-1: that sequence's slot is left alone): the slot
+ * is then what edgehip_upload_keylines(ctx, seq, slot, records, kn, NULL, 0) of the entry's records leaves — edgehip_depth_fill,
+ * edgehip_surface_view_capture and edgehip_minimizer_rv_kf run on an older key frame without a host copy.  The ordinals are checked on
+ * the host against a synchronising read of the lists' counts, so the call synchronises first; the copy itself is enqueued and not
+ * waited for.  EDGEHIP_ERR_ARG for an ordinal a list does not hold: nothing changes. */
+int edgehip_keyframe_list_restore(edgehip_ctx *ctx, int slot, const int32_t *ordinals /* [nseq] */);
 
 /* ---- measurement ------------------------------------------------------------------------------------- */
 /* Names of the kernel groups timed by the built-in HIP-event profiler, and their accumulated device time.

@@ -1,13 +1,14 @@
 """GlobalConfig files in the reference's format, written from an edgehip Params struct (tests, bench.py, examples)."""
 
 
-def write_global_config(path, p, log_file="", tray_file="", save_log=0, camera_type=3, drop=(), dataset=None, imu=None, stereo=None, gpu=None, affinity=None):
+def write_global_config(path, p, log_file="", tray_file="", save_log=0, camera_type=3, drop=(), dataset=None, imu=None, stereo=None, gpu=None, affinity=None, keyframes=None):
     """A GlobalConfig file in the reference's format (app/rebvorun/GlobalConfig_EuRoC) from a Params struct.
     `drop` lists "Section/Key" entries to leave out (missing-key error tests).  `imu` = dict(mode=1|2, file=..., se3=...,
     time_scale=..., plus any key of the &IMU section to override) switches the IMU branch on.  `stereo` = dict(dir=..., file=...,
     ppx=, ppy=, zfx=, zfy=) sets StereoAvaiable with the pair camera's list and the &Stereo intrinsics.  `gpu` = dict(device=,
     group=, size=, mono=, tracker_precision=) writes the optional &GPU section (Device, BatchGroup, BatchSize, MonoUpload, TrackerPrecision: rebvo_amd/host/include/rebvo/rebvo.h).
-    `affinity` = (CamaraT1, CamaraT2, CamaraT3) writes &ProcesorConfig with SetAffinity=1."""
+    `affinity` = (CamaraT1, CamaraT2, CamaraT3) writes &ProcesorConfig with SetAffinity=1.  `keyframes` = KFSavePercent sets
+    TrackKeyFrames=1 with that value."""
     sec = {
         "Detector": [("Sigma0", p.sigma0), ("KSigma", p.ksigma), ("ReferencePoints", p.reference_points),
                      ("MaxPoints", p.max_points), ("TrackPoints", p.track_points), ("DetectorThresh", p.detector_thresh),
@@ -31,6 +32,8 @@ def write_global_config(path, p, log_file="", tray_file="", save_log=0, camera_t
                   ("TrayFile", tray_file), ("TrackKeyFrames", 0), ("StereoAvaiable", 0)],
         "IMU": [("ImuMode", 0)],
     }
+    if keyframes is not None:
+        sec["REBVO"] = [(k, (1 if k == "TrackKeyFrames" else v)) for k, v in sec["REBVO"]] + [("KFSavePercent", keyframes)]
     if imu is not None:       # the &IMU section of app/rebvorun/GlobalConfig_EuRoC
         keys = dict(TimeDesinc=0, InitBias=1, InitBiasFrameNum=10, BiasHintX=0.0188, BiasHintY=0.0037, BiasHintZ=0.0776,
                     GiroMeasStdDev=1.6968e-04, GiroBiasStdDev=1.9393e-05, AcelMeasStdDev=2.0000e-3, g_module=9.8,

@@ -1,0 +1,92 @@
+// keyframe_track.h — what keyframe_track.hip (the current key frame and its repair) and keyframe_list.hip (the ring of retired key
+// frames) share: the per-sequence key-frame state, the list's device view, and the store behind edgehip_ctx::kftrack.
+#pragma once
+#include "ctx.h"
+
+#include <vector>
+
+namespace edgehip {
+
+struct KfSeq {
+    edgehip_kf_pose pose;
+    int32_t kn, kf_count, active, do_insert;
+    double Ef[9], Eb[9];     // forwardCorrectAugmentate's / correctAugmentate's E of the running frame
+};
+
+// ---- the key-frame list (keyframe_list.hip) ------------------------------------------------------------------------------------------
+// Per sequence a ring of `capacity` entries; the key frame with ordinal j (the j-th the sequence ever took, from 0) lives in ring
+// position j % capacity.  An entry is a header and room for max_points 168-byte records; headers and records are two arrays, so that
+// every entry's records start at a multiple of 16 bytes (the stride is max_points * 168 rounded up to 16: an odd max_points alone
+// would not give that).  Memory: (stride + 264 B) * capacity * nseq.
+struct KfListHdr {
+    edgehip_kf_pose pose;
+    int32_t kn, ordinal;
+};
+struct KfListSeq {
+    int32_t first, held, overwritten;   // the held ordinals are [first, first + held); entries lost to the ring so far
+    int32_t retire_kn, retire_pos;      // of the retirement under way: KeyLines of the outgoing key frame (-1: none) and its ring position
+    int32_t pad;
+};
+struct KfListDev {           // by value into the kernels; hdr == nullptr: the list is off
+    uint8_t *rec;            // [nseq][capacity] entries of `stride` bytes
+    KfListHdr *hdr;          // [nseq][capacity]
+    KfListSeq *ls;           // [nseq]
+    size_t stride;
+    int capacity, cap;       // ring entries; max_points
+};
+
+// The outgoing key frame's header goes into the list and the sequence's retirement is posted for k_kf_retire.  Called by the one thread
+// that is about to overwrite ks[seq] (k_kf_decide, k_kf_retire_mark), BEFORE it does: `k` is the outgoing state.
+__device__ inline void kf_list_retire_head(const KfListDev &l, int seq, const KfSeq &k, bool retire) {
+    KfListSeq &q = l.ls[seq];
+    if (!retire || k.kf_count <= 0) { q.retire_kn = -1; return; }
+    const int ordinal = k.kf_count - 1, pos = ordinal % l.capacity;
+    KfListHdr &h = l.hdr[(size_t)seq * l.capacity + pos];
+    h.pose = k.pose;
+    h.kn = max(0, min(k.kn, l.cap));
+    h.ordinal = ordinal;
+    if (q.held == l.capacity) { q.first++; q.overwritten++; }
+    else q.held++;
+    q.retire_kn = h.kn;
+    q.retire_pos = pos;
+}
+
+}  // namespace edgehip
+
+struct edgehip_ctx::KfTrack {
+    double save_percent = 0;
+    int save_keyframes = 0;
+    bool in_driver = true;            // edgehip_process_frame runs the steps (enable == 1); false: the store and the stage-level entry points alone
+    int use_lds = 1;
+    int np2cap = 1;
+    std::vector<void *> dev;          // every device allocation
+    std::vector<edgehip::KlSoA> kl;   // [nseq] host copies of the key frames' array pointers
+    edgehip::KlSoA *kl_dev = nullptr; // [nseq]
+    edgehip::KfSeq *ks = nullptr;     // [nseq]
+    edgehip_kf_track *rec = nullptr;  // [nseq]
+    int32_t *table = nullptr;         // [nseq][cap] buildForwardMatch's fowMatch
+    double *dist = nullptr;           // [nseq][cap]
+    uint32_t *keys = nullptr;         // [nseq][np2cap]
+    edgehip_keyline *aos = nullptr;   // [cap] staging of upload / download
+    // a caller's Pose / Pos, pose blocks and mask on their way to an in-stream kernel
+    double *pose12_dev = nullptr, *pose12_host = nullptr;           // [nseq][12]
+    edgehip_kf_pose *blk_dev = nullptr, *blk_host = nullptr;        // [nseq]
+    uint8_t *mask_dev = nullptr, *mask_host = nullptr;              // [nseq]
+    hipEvent_t ev = nullptr;
+    bool busy = false;
+    // the key-frame list (keyframe_list.hip); list.hdr == nullptr: off
+    edgehip::KfListDev list = {};
+    void *list_arena = nullptr;       // records | headers | per-sequence state | restore requests
+    int32_t *list_req_dev = nullptr, *list_req_host = nullptr;      // [nseq] edgehip_keyframe_list_restore's ring positions
+};
+
+namespace edgehip {
+
+void kf_list_free(edgehip_ctx *c);                   // behind a synchronisation of c->stream; no-op when off
+int kf_list_reset_enqueue(edgehip_ctx *c);           // edgehip_reset: no entries (no-op when off)
+// Behind a k_kf_decide that was given the list: the records of the posted retirements, before k_kf_copy overwrites them (no-op when off).
+int kf_list_retire_enqueue(edgehip_ctx *c);
+// edgehip_upload_keyframe: posts the retirement of sequence `seq`'s key frame (if it has one) and enqueues its records (no-op when off).
+int kf_list_retire_one_enqueue(edgehip_ctx *c, int seq);
+
+}  // namespace edgehip

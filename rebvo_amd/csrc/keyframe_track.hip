@@ -25,7 +25,7 @@
 // match is left alone with guard bit 2.  Every chain walk is capped at the length of the list it walks: on finite p_m a walk strictly
 // decreases its distance and ends before that; a NaN p_m inside a link cycle (where the reference never returns) ends at the cap and sets
 // guard bit 1.
-#include "ctx.h"
+#include "keyframe_track.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -38,12 +38,6 @@ namespace edgehip {
 constexpr int kKfThreads = 256;          // per-KeyLine kernels
 constexpr int kKfAugThreads = 1024;      // phase 2: one workgroup per sequence
 constexpr int kKfLdsKeys = 16384;        // keys that fit 64 KB of LDS
-
-struct KfSeq {
-    edgehip_kf_pose pose;
-    int32_t kn, kf_count, active, do_insert;
-    double Ef[9], Eb[9];     // forwardCorrectAugmentate's / correctAugmentate's E of the running frame
-};
 
 struct KfArgs {
     const KlSoA *slot_kl;    // [nseq] KeyLines of the frame slot
@@ -353,8 +347,11 @@ __global__ __launch_bounds__(kKfAugThreads) void k_kf_augment(KfArgs a) {
 // mode 0: the sequences of `mask` (null: all), pose block from `pose_in` or, null, from the frame's nav record and seq_state.K;
 // mode 1: sequences without a key frame (rebvo_second_t.cpp:156-162: K = 1, the old frame's nav record);
 // mode 2: sequences whose repaired back count fell below min(TrackPoints, KNum) * KFSavePercent (:591-596).
+// With the key-frame list on (list.hdr), the header of a key frame that is about to be replaced goes into the list here, where its pose
+// block, kn and ordinal are last seen; k_kf_retire (keyframe_list.hip) takes its records before k_kf_copy runs.
 __global__ void k_kf_decide(KfArgs a, const SeqDev *__restrict__ seqs, const edgehip_nav *__restrict__ nav, const uint8_t *__restrict__ mask,
-                            const edgehip_kf_pose *__restrict__ pose_in, int mode, int track_points, double save_percent, int save_keyframes) {
+                            const edgehip_kf_pose *__restrict__ pose_in, int mode, int track_points, double save_percent, int save_keyframes,
+                            KfListDev list) {
     const int seq = blockIdx.x * blockDim.x + threadIdx.x;
     if (seq >= a.nseq) return;
     KfSeq &k = a.ks[seq];
@@ -367,6 +364,7 @@ __global__ void k_kf_decide(KfArgs a, const SeqDev *__restrict__ seqs, const edg
     k.do_insert = ins;
     if (mode == 1) r.inserted = ins;
     else if (ins) r.inserted = 1;
+    if (list.hdr) kf_list_retire_head(list, seq, k, ins != 0);
     if (ins) {
         if (pose_in) {
             k.pose = pose_in[seq];
@@ -443,33 +441,11 @@ __global__ __launch_bounds__(kKfThreads) void k_kf_unpack(KlSoA k, int kn, const
 
 using namespace edgehip;
 
-struct edgehip_ctx::KfTrack {
-    double save_percent = 0;
-    int save_keyframes = 0;
-    bool in_driver = true;            // edgehip_process_frame runs the steps (enable == 1); false: the store and the stage-level entry points alone
-    int use_lds = 1;
-    int np2cap = 1;
-    std::vector<void *> dev;          // every device allocation
-    std::vector<KlSoA> kl;            // [nseq] host copies of the key frames' array pointers
-    KlSoA *kl_dev = nullptr;          // [nseq]
-    KfSeq *ks = nullptr;              // [nseq]
-    edgehip_kf_track *rec = nullptr;  // [nseq]
-    int32_t *table = nullptr;         // [nseq][cap]
-    double *dist = nullptr;           // [nseq][cap]
-    uint32_t *keys = nullptr;         // [nseq][np2cap]
-    edgehip_keyline *aos = nullptr;   // [cap] staging of upload / download
-    // a caller's Pose / Pos, pose blocks and mask on their way to an in-stream kernel
-    double *pose12_dev = nullptr, *pose12_host = nullptr;           // [nseq][12]
-    edgehip_kf_pose *blk_dev = nullptr, *blk_host = nullptr;        // [nseq]
-    uint8_t *mask_dev = nullptr, *mask_host = nullptr;              // [nseq]
-    hipEvent_t ev = nullptr;
-    bool busy = false;
-};
-
 void edgehip::kf_track_free(edgehip_ctx *c) {
     auto *d = c->kftrack;
     if (!d) return;
     (void)hipStreamSynchronize(c->stream);
+    kf_list_free(c);
     for (void *q : d->dev) (void)hipFree(q);
     if (d->pose12_host) (void)hipHostFree(d->pose12_host);
     if (d->blk_host) (void)hipHostFree(d->blk_host);
@@ -546,7 +522,7 @@ int edgehip::kf_track_reset_enqueue(edgehip_ctx *c) {
     if (!d) return 0;
     EH_CHECK(hipMemsetAsync(d->ks, 0, sizeof(KfSeq) * c->plan.nseq, c->stream));
     EH_CHECK(hipMemsetAsync(d->rec, 0, sizeof(edgehip_kf_track) * c->plan.nseq, c->stream));
-    return 0;
+    return kf_list_reset_enqueue(c);
 }
 
 static KfArgs kf_args(edgehip_ctx *c, int slot) {
@@ -603,8 +579,9 @@ int edgehip::kf_frame_begin_enqueue(edgehip_ctx *c, int slot_old) {   // rebvo_s
     if (!c->kftrack->in_driver) return 0;
     KfArgs a = kf_args(c, slot_old);
     hipLaunchKernelGGL(k_kf_decide, kf_seq_grid(c), dim3(64), 0, c->stream, a, (const SeqDev *)c->seq, (const edgehip_nav *)c->nav_dev,
-                       (const uint8_t *)nullptr, (const edgehip_kf_pose *)nullptr, 1, 0, 0.0, 0);
+                       (const uint8_t *)nullptr, (const edgehip_kf_pose *)nullptr, 1, 0, 0.0, 0, c->kftrack->list);
     EH_LAUNCH_CHECK();
+    if (int e = kf_list_retire_enqueue(c)) return e;
     hipLaunchKernelGGL(k_kf_copy, kf_grid(c), dim3(kKfThreads), 0, c->stream, a);
     EH_LAUNCH_CHECK();
     return 0;
@@ -627,8 +604,9 @@ int edgehip::kf_frame_end_enqueue(edgehip_ctx *c, int slot_new) {   // :591-596
     auto *d = c->kftrack;
     KfArgs a = kf_args(c, slot_new);
     hipLaunchKernelGGL(k_kf_decide, kf_seq_grid(c), dim3(64), 0, c->stream, a, (const SeqDev *)c->seq, (const edgehip_nav *)c->nav_dev,
-                       (const uint8_t *)nullptr, (const edgehip_kf_pose *)nullptr, 2, c->p.track_points, d->save_percent, d->save_keyframes);
+                       (const uint8_t *)nullptr, (const edgehip_kf_pose *)nullptr, 2, c->p.track_points, d->save_percent, d->save_keyframes, d->list);
     EH_LAUNCH_CHECK();
+    if (int e = kf_list_retire_enqueue(c)) return e;
     hipLaunchKernelGGL(k_kf_copy, kf_grid(c), dim3(kKfThreads), 0, c->stream, a);
     EH_LAUNCH_CHECK();
     return 0;
@@ -664,8 +642,9 @@ int edgehip_keyframe_insert(edgehip_ctx *c, int slot, const uint8_t *mask, const
     }
     KfArgs a = kf_args(c, slot);
     hipLaunchKernelGGL(k_kf_decide, kf_seq_grid(c), dim3(64), 0, c->stream, a, (const SeqDev *)c->seq, (const edgehip_nav *)c->nav_dev,
-                       (const uint8_t *)(mask ? d->mask_dev : nullptr), (const edgehip_kf_pose *)(pose ? d->blk_dev : nullptr), 0, 0, 0.0, 0);
+                       (const uint8_t *)(mask ? d->mask_dev : nullptr), (const edgehip_kf_pose *)(pose ? d->blk_dev : nullptr), 0, 0, 0.0, 0, d->list);
     EH_LAUNCH_CHECK();
+    if (int e = kf_list_retire_enqueue(c)) return e;
     hipLaunchKernelGGL(k_kf_copy, kf_grid(c), dim3(kKfThreads), 0, c->stream, a);
     EH_LAUNCH_CHECK();
     return slot_read_done(c, slot);
@@ -762,6 +741,7 @@ int edgehip_upload_keyframe(edgehip_ctx *c, int seq, const edgehip_keyline *kl, 
     KfSeq k;
     EH_CHECK(hipMemcpyAsync(&k, d->ks + seq, sizeof k, hipMemcpyDeviceToHost, c->stream));
     EH_CHECK(hipStreamSynchronize(c->stream));
+    if (int e = kf_list_retire_one_enqueue(c, seq)) return e;   // the outgoing key frame into the list, before its arrays are overwritten
     k.pose = *pose;
     k.kn = kn;
     k.kf_count++;

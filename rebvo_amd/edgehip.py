@@ -232,8 +232,14 @@ class KfTrack(C.Structure):
                 ("inserted", C.c_int32), ("kf_count", C.c_int32), ("guard", C.c_int32), ("kf_kn", C.c_int32)]
 
 
+class KfListInfo(C.Structure):
+    """edgehip_kf_list_info: the key frames taken, and the ordinals [first, first + held) the list holds."""
+    _fields_ = [("kf_count", C.c_int32), ("first", C.c_int32), ("held", C.c_int32), ("overwritten", C.c_int32)]
+
+
 KF_POSE_DTYPE = np.dtype(KfPose)
 KF_TRACK_DTYPE = np.dtype(KfTrack)
+KF_LIST_INFO_DTYPE = np.dtype(KfListInfo)
 NAV_DTYPE = np.dtype(Nav)   # numpy view of edgehip_nav (same offsets as the ctypes struct)
 assert NAV_DTYPE.itemsize == C.sizeof(Nav)
 
@@ -267,6 +273,8 @@ EXPORTS = [
     "edgehip_match_one_pass",
     "edgehip_keyframe_track_enable", "edgehip_keyframe_insert", "edgehip_keyframe_build_forward_match", "edgehip_keyframe_forward_correct",
     "edgehip_keyframe_back_correct", "edgehip_read_keyframe_track", "edgehip_download_keyframe", "edgehip_upload_keyframe",
+    "edgehip_keyframe_set_save", "edgehip_keyframe_list_enable", "edgehip_keyframe_list_info", "edgehip_download_keyframe_list",
+    "edgehip_download_keyframe_list_batch", "edgehip_keyframe_list_restore",
 ]
 
 _lib = None
@@ -304,6 +312,70 @@ def build_undistort_map(params):
 
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+# ---- the reference's key-frame file (keyframe::saveKeyframes2File / loadKeyframesFromFile; no GPU, no library) ----
+# int32 kfnum, then per key frame: the pose block (t, K, Rot[9] row-major, RotLie[3], Vel[3], Pose[9], PoseLie[3], Pos[3]: 32 doubles),
+# double max_r (what build_field was last given: SearchRange), the raw cam_model (72 B), int32 kn, kn 168-byte KeyLine records.
+KF_FILE_CAM_DTYPE = np.dtype([("pp", "<f4", (2,)), ("zf", "<f4", (2,)), ("zfm", "<f8"), ("Kc", "<f8", (5,)), ("w", "<i4"), ("h", "<i4")])
+assert KF_FILE_CAM_DTYPE.itemsize == 72 and KF_POSE_DTYPE.itemsize == 256
+
+
+def keyframe_file_camera(params):
+    """The cam_model the reference builds from the configuration: pp, zf narrowed to float, zfm = (zf.x + zf.y) / 2 computed in float."""
+    cam = np.zeros((), KF_FILE_CAM_DTYPE)
+    cam["pp"] = (params.ppx, params.ppy)
+    cam["zf"] = (params.zfx, params.zfy)
+    cam["zfm"] = np.float32((cam["zf"][0] + cam["zf"][1]) / np.float32(2))
+    cam["Kc"] = list(params.kc)
+    cam["w"], cam["h"] = params.w, params.h
+    return cam
+
+
+def write_keyframe_file(path, keyframes, params, max_r=None):
+    """keyframes: a sequence of (KfPose, KeyLine records) pairs, oldest first; params: the Params the camera and max_r (SearchRange, unless
+    given) come from.  Writes the records as they are, so bytes 36..39 of each are whatever the array holds (zero from the device)."""
+    cam = keyframe_file_camera(params)
+    max_r = float(params.search_range if max_r is None else max_r)
+    with open(path, "wb") as f:
+        f.write(np.int32(len(keyframes)).tobytes())
+        for pose, kl in keyframes:
+            kl = np.ascontiguousarray(kl, dtype=KEYLINE_DTYPE)
+            f.write(bytes(pose))
+            f.write(np.float64(max_r).tobytes())
+            f.write(cam.tobytes())
+            f.write(np.int32(len(kl)).tobytes())
+            f.write(kl.tobytes())
+
+
+def read_keyframe_file(path):
+    """-> a list of dicts (pose: KfPose, max_r, camera: KF_FILE_CAM_DTYPE scalar, kl: KeyLine records).  ValueError for a file that ends
+    early or holds a negative count."""
+    with open(path, "rb") as f:
+        data = f.read()
+    at = 0
+
+    def take(n, what):
+        nonlocal at
+        if n < 0 or at + n > len(data):
+            raise ValueError(f"{path}: truncated key-frame file ({what} at byte {at})")
+        at += n
+        return data[at - n:at]
+
+    kfnum = int(np.frombuffer(take(4, "kfnum"), "<i4")[0])
+    if kfnum < 0:
+        raise ValueError(f"{path}: negative key-frame count")
+    out = []
+    for i in range(kfnum):
+        pose = KfPose.from_buffer_copy(take(256, f"pose block {i}"))
+        max_r = float(np.frombuffer(take(8, f"max_r {i}"), "<f8")[0])
+        cam = np.frombuffer(take(72, f"camera {i}"), KF_FILE_CAM_DTYPE)[0].copy()
+        kn = int(np.frombuffer(take(4, f"kn {i}"), "<i4")[0])
+        if kn < 0:
+            raise ValueError(f"{path}: negative KeyLine count in key frame {i}")
+        kl = np.frombuffer(take(kn * KEYLINE_DTYPE.itemsize, f"records {i}"), KEYLINE_DTYPE).copy()
+        out.append(dict(pose=pose, max_r=max_r, camera=cam, kl=kl))
+    return out
 
 
 class EdgeHip:
@@ -1100,6 +1172,46 @@ class EdgeHip:
     def upload_keyframe(self, seq, kl, pose):
         kl = np.ascontiguousarray(kl, dtype=KEYLINE_DTYPE)
         self._ck(self.lib.edgehip_upload_keyframe(self.ctx, seq, kl.ctypes.data_as(C.c_void_p), len(kl), C.byref(pose)))
+
+    def keyframe_set_save(self, save_keyframes):
+        """REBVO::saveKeyframes at run time (startKeyFrames / endKeyFrames): from the next frame on; key frames and list stay."""
+        self._ck(self.lib.edgehip_keyframe_set_save(self.ctx, int(bool(save_keyframes))))
+
+    # ---- the key-frame list (REBVO::kf_list) ----
+    def keyframe_list_enable(self, capacity):
+        """A ring of `capacity` retired key frames per sequence (0 frees it); needs keyframe_track_enable."""
+        self._ck(self.lib.edgehip_keyframe_list_enable(self.ctx, int(capacity)))
+
+    def keyframe_list_info(self):
+        """-> structured array [nseq] (KF_LIST_INFO_DTYPE): kf_count, first, held, overwritten."""
+        out = np.zeros(self.nseq, KF_LIST_INFO_DTYPE)
+        self._ck(self.lib.edgehip_keyframe_list_info(self.ctx, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def download_keyframe_list(self, seq, ordinal):
+        """seq, ordinal ints -> (KeyLine records [kn], KfPose) of that list entry; sequences of both -> a list of such pairs, through
+        the batch call."""
+        single = np.isscalar(seq)
+        seqs = np.atleast_1d(np.asarray(seq, np.int32)).copy()
+        ords = np.atleast_1d(np.asarray(ordinal, np.int32)).copy()
+        assert seqs.shape == ords.shape and seqs.ndim == 1 and len(seqs) >= 1
+        n = len(seqs)
+        kls = [np.zeros(self.cap, KEYLINE_DTYPE) for _ in range(n)]
+        ptrs = (C.c_void_p * n)(*[k.ctypes.data for k in kls])
+        kn = np.zeros(n, np.int32)
+        poses = (KfPose * n)()
+        if single:
+            self._ck(self.lib.edgehip_download_keyframe_list(self.ctx, int(seqs[0]), int(ords[0]), C.c_void_p(kls[0].ctypes.data), kn.ctypes.data_as(C.c_void_p), poses))
+        else:
+            self._ck(self.lib.edgehip_download_keyframe_list_batch(self.ctx, n, seqs.ctypes.data_as(C.c_void_p), ords.ctypes.data_as(C.c_void_p),
+                                                                   ptrs, kn.ctypes.data_as(C.c_void_p), poses))
+        out = [(kls[j][:kn[j]].copy(), KfPose.from_buffer_copy(poses[j])) for j in range(n)]
+        return out[0] if single else out
+
+    def keyframe_list_restore(self, slot, ordinals):
+        """List entry ordinals[seq] of every sequence back into ring slot `slot` (-1: leave that sequence's slot alone)."""
+        o = np.ascontiguousarray(np.broadcast_to(np.asarray(ordinals, np.int32), (self.nseq,))).copy()
+        self._ck(self.lib.edgehip_keyframe_list_restore(self.ctx, slot, o.ctypes.data_as(C.c_void_p)))
 
     def download_plane(self, seq, which):
         idx = {"img0": 0, "img1": 1, "dog": 2, "dx": 3, "dy": 4}[which]

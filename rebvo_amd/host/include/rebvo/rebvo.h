@@ -63,6 +63,7 @@
 #endif
 
 struct edgehip_ctx;
+struct edgehip_params;
 
 namespace rebvo {
 
@@ -399,11 +400,14 @@ namespace customCam {
 struct CustomCamPipeBuffer {
     std::shared_ptr<Image<RGB24Pixel>> img;
     double timestamp = 0;
+    bool save_kf = false;   // (mirror only) REBVO::saveKeyframes when the frame was handed over: the frame is tracked with that flag
 };
 }  // namespace customCam
 
 constexpr int CBUFSIZE = 0x08;
 constexpr int CCAMBUFSIZE = 0x04;
+
+class keyframe;   // rebvo/keyframe.h (included at the end of this header)
 
 class REBVO {
     REBVOParameters params;
@@ -415,6 +419,7 @@ class REBVO {
     Pipeline<PipeBuffer> pipe;
     std::atomic_bool system_reset;
     std::atomic_bool saveImg{false};
+    std::atomic_bool saveKeyframes{false};   // rebvo.h:420 of the reference; starts false (rebvo.cpp:236)
     int snap_n = 0;
     std::atomic_bool frame_by_frame{false}, frame_by_frame_advance{false};
     Pipeline<customCam::CustomCamPipeBuffer> cam_pipe;
@@ -502,9 +507,17 @@ public:
     void ensureHostViews(PipeBuffer &pb, bool keylines);
     void Reset() { system_reset = true; }
     bool Running() { return !quit; }
-    void startKeyFrames() {}
-    void endKeyFrames() {}
-    bool toggleKeyFrames() { return false; }
+    // REBVO::saveKeyframes (rebvo.h:476-478 of the reference): while it is set, TrackKeyFrames = 1 takes a new key frame whenever the
+    // criterion of rebvo_second_t.cpp:591-596 holds (the first key frame is taken without it).  A frame is tracked with the value the
+    // flag had when it was handed over (releaseCustomCamBuffer); the device keeps one flag per context (edgehip_keyframe_set_save), so
+    // in a batch group a step saves when any member's frame of that step asks for it: members are expected to switch together.
+    void startKeyFrames() { saveKeyframes = true; }
+    void endKeyFrames() { saveKeyframes = false; }
+    bool toggleKeyFrames() { return saveKeyframes = !saveKeyframes; }
+    // The key frames taken so far (rebvo.h:437 of the reference), oldest first, with TrackKeyFrames = 1 (ImuMode 0, no stereo pair; other
+    // objects ignore the key and the list stays empty).  Retired key frames arrive as the steps that replaced them complete; CleanUp()
+    // appends the current one.  As upstream, reading it while the object runs is unsynchronised.
+    std::vector<keyframe> kf_list;
     // frame-by-frame mode: no new frame is taken from the camera until advanceFrameByFrame() (rebvo.h:481-488, rebvo_first_t.cpp:154-159)
     bool toggleFrameByFrame() { return frame_by_frame = !frame_by_frame; }
     bool advanceFrameByFrame() { return frame_by_frame_advance = true; }
@@ -534,6 +547,7 @@ public:
         return true;
     }
     void releaseCustomCamBuffer() {
+        if (cam_cur) cam_cur->save_kf = saveKeyframes;
         if (group && cam_cur) groupFrameWritten(cam_cur);   // (a mono frame's 8-bit plane, on this thread: src/mono_pack.cpp)
         cam_cur = nullptr;
         cam_pipe.ReleaseBuffer(0);
@@ -570,5 +584,11 @@ public:
     Vector3 getCam2ImuPos();
 };
 
+// (mirror only) The device library's parameters for a configuration — what Init() hands edgehip_create (include/edgehip.h) — for an
+// application that runs C-ABI stages of its own beside the objects (examples/keyframe_replay.cpp --map).
+void edgehipParams(const REBVOParameters &p, edgehip_params &out);
+
 }  // namespace rebvo
+
+#include "rebvo/keyframe.h"   // REBVO::kf_list's element type
 #endif

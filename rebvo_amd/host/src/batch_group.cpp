@@ -162,6 +162,19 @@ public:
     // edgehip_depth_fill on `slot` (and edgehip_depth_surface when dsp is on), then the products of sequences seq[j] into dst[j], sdst[j], idst[j]
     int dfGrids(int slot, const std::vector<int32_t> &seq, std::vector<DepthGrid *> &dst, std::vector<DepthSurface *> &sdst,
                 std::vector<DepthImage *> &idst);
+    // TrackKeyFrames = 1 (the same for every member; ImuMode 0, no stereo pair): key-frame tracking inside edgehip_process_frame and the
+    // device's key-frame list, drained into the members' REBVO::kf_list at every completed step.  The drain reads the lists' counts,
+    // which waits for everything enqueued (kfDrain): while tracking is on, the steps launched ahead have finished by the time a step's
+    // records are handed over, and the group runs one step deep in effect.  A step retires at most one key frame per sequence (the
+    // insertion rule at its end; the first-key-frame rule at its begin replaces nothing), and between two drains at most three steps
+    // are enqueued (threadMain keeps at most two pending behind the one it completes): a ring of kKfListCapacity = 4 never overwrites
+    // an entry that has not been moved.
+    static constexpr int kKfListCapacity = 4;
+    bool kf_track = false;
+    double kf_pct = 0;
+    int kf_save = 0;               // the context's save flag (edgehip_keyframe_set_save)
+    std::vector<int32_t> kf_next;  // [cap] the next ordinal to move into the member's kf_list
+    int kfDrain(int only_seat, bool with_current);   // only_seat < 0: every running member; with_current: the current key frame too (CleanUp)
     int cb_depth = 2;              // steps in flight when somebody has a callback (REBVO_GROUP_CB_DEPTH=1: the round-5 behaviour, A/B)
 
     void threadMain();
@@ -218,6 +231,9 @@ bool REBVO::groupAttach() {
     if (dfill) { dsp.surface = params.DF_Surface != 0; dsp.image_mode = params.DF_DenseImage; }
     const int em_what = (params.EM_PointCloud ? EDGEHIP_ROS_POINTS : 0) | (params.EM_KeylineMsg ? EDGEHIP_ROS_KEYLINES : 0);
     const bool em_list = params.EM_KeyLineList != 0;
+    // TrackKeyFrames: ImuMode 0 and no stereo pair (the device's IMU branch refuses it; other objects ignore the key, as before)
+    const bool kf_track = params.TrackKeyFrames && !imu_mode && !stereo;
+    const double kf_pct = kf_track ? params.KFSavePercent : 0;
     auto fail = [&](const std::string &msg) {
         last_error = msg;
         std::cout << last_error << "\n";
@@ -272,6 +288,11 @@ bool REBVO::groupAttach() {
         g->dfill = dfill;
         g->dfp = dfp;
         g->dsp = dsp;
+        g->kf_track = kf_track;
+        g->kf_pct = kf_pct;
+        g->kf_next.assign(want, 0);
+        if (rc == 0 && kf_track) rc = edgehip_keyframe_track_enable(g->hip, 1, kf_pct, 0);   // (REBVO::saveKeyframes starts false)
+        if (rc == 0 && kf_track) rc = edgehip_keyframe_list_enable(g->hip, BatchGroup::kKfListCapacity);
         if (rc == 0 && dfill) rc = edgehip_depth_fill_enable(g->hip, &dfp);
         if (rc == 0 && (dsp.surface || dsp.image_mode)) rc = edgehip_depth_surface_enable(g->hip, &dsp);
         g->frame_bytes = (size_t)params.ImageSize.w * params.ImageSize.h * sizeof(RGB24Pixel);
@@ -313,6 +334,8 @@ bool REBVO::groupAttach() {
             return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same &DepthFiller parameters");
         if (std::memcmp(&g->dsp, &dsp, sizeof dsp) != 0)
             return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same &DepthFiller Surface and DenseImage");
+        if (g->kf_track != kf_track || g->kf_pct != kf_pct)
+            return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same TrackKeyFrames and KFSavePercent");
         if (g->em_what != em_what || g->em_list != em_list)
             return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same &EdgeMapOutput PointCloud, KeylineMsg and KeyLineList");
     }
@@ -378,7 +401,7 @@ void REBVO::FeedThread(REBVO *cf) {
     auto slot = [&](double stamp) -> customCam::CustomCamPipeBuffer * {
         customCam::CustomCamPipeBuffer *b = nullptr;
         while (!cf->quit && (b = cf->cam_pipe.RequestBufferTimeoutable(0, 0.01)) == nullptr) {}
-        if (b) b->timestamp = stamp;
+        if (b) { b->timestamp = stamp; b->save_kf = cf->saveKeyframes; }
         return b;
     };
     while (!cf->quit) {
@@ -500,6 +523,8 @@ void REBVO::BatchGroup::closeSeat(Seat &st) {
     // shutdown of one member: the frame still held for it is not delivered (as in the reference); pass the quit flag on
     REBVO *cf = st.cf;
     if (st.kl_pinned) pinKeyLines(st, false);
+    if (kf_track && !failed && st.frames > 0 && kfDrain((int)(&st - seats.data()), true) != 0)   // what is left of its list, and its current key frame
+        std::cout << "REBVO(hip): key-frame list: " << edgehip_last_error() << "\n";
     if (st.chold) { cf->cam_pipe.ReleaseBufferAt(1, st.chold); st.chold = nullptr; }
     if (st.cbuf) { cf->cam_pipe.ReleaseBufferAt(1, st.cbuf); st.cbuf = nullptr; }
     for (customCam::CustomCamPipeBuffer *&pb : st.pair_of)   // oldest first (the ring hands buffers out and takes them back in order)
@@ -520,6 +545,63 @@ void REBVO::BatchGroup::closeSeat(Seat &st) {
         st.closed = true;
     }
     cv.notify_all();
+}
+
+// Newly retired key frames out of the device's list into the members' kf_list: one read of the lists' counts, one batch download
+// (edgehip_keyframe_list_info synchronises with everything enqueued, the steps in flight included).
+int REBVO::BatchGroup::kfDrain(int only_seat, bool with_current) {
+    std::vector<edgehip_kf_list_info> info(cap);
+    int rc = edgehip_keyframe_list_info(hip, info.data());
+    if (rc != 0) return rc;
+    auto fill = [](keyframe &kf, const edgehip_kf_pose &p, REBVO *cf) {
+        kf.t = p.t; kf.K = p.K;
+        for (int i = 0; i < 9; i++) { kf.Rot(i / 3, i % 3) = p.Rot[i]; kf.Pose(i / 3, i % 3) = p.Pose[i]; }
+        for (int i = 0; i < 3; i++) { kf.RotLie[i] = p.RotLie[i]; kf.Vel[i] = p.Vel[i]; kf.PoseLie[i] = p.PoseLie[i]; kf.Pos[i] = p.Pos[i]; }
+        kf.camera = cf->cam;
+        kf.max_r = (int)cf->params.SearchRange;   // global_tracker::getMaxSRadius(): what build_field was last given
+    };
+    std::vector<int32_t> rs, ro;
+    for (int i = 0; i < cap; i++) {
+        if (!seats[i].running || (only_seat >= 0 && i != only_seat)) continue;
+        const int end = info[i].first + info[i].held;
+        for (int j = std::max(kf_next[i], info[i].first); j < end; j++) { rs.push_back(i); ro.push_back(j); }
+    }
+    const size_t n = rs.size();
+    if (n) {
+        std::vector<keyframe> got(n);
+        std::vector<edgehip_keyline *> dst(n);
+        std::vector<int32_t> kn(n);
+        std::vector<edgehip_kf_pose> pose(n);
+        for (size_t j = 0; j < n; j++) {
+            got[j].kl.resize((size_t)hp.max_points);
+            dst[j] = reinterpret_cast<edgehip_keyline *>(got[j].kl.data());
+        }
+        rc = edgehip_download_keyframe_list_batch(hip, (int)n, rs.data(), ro.data(), dst.data(), kn.data(), pose.data());
+        if (rc != 0) return rc;
+        for (size_t j = 0; j < n; j++) {
+            REBVO *cf = seats[rs[j]].cf;
+            got[j].kl.resize((size_t)kn[j]);
+            got[j].kl.shrink_to_fit();
+            fill(got[j], pose[j], cf);
+            cf->kf_list.push_back(std::move(got[j]));
+            kf_next[rs[j]] = ro[j] + 1;
+        }
+    }
+    if (with_current)
+        for (int i = 0; i < cap; i++) {
+            if (!seats[i].running || (only_seat >= 0 && i != only_seat) || info[i].kf_count < 1) continue;
+            keyframe kf;
+            kf.kl.resize((size_t)hp.max_points);
+            int32_t kn = 0;
+            edgehip_kf_pose pose;
+            rc = edgehip_download_keyframe(hip, i, reinterpret_cast<edgehip_keyline *>(kf.kl.data()), &kn, &pose, nullptr);
+            if (rc != 0) return rc;
+            kf.kl.resize((size_t)kn);
+            kf.kl.shrink_to_fit();
+            fill(kf, pose, seats[i].cf);
+            seats[i].cf->kf_list.push_back(std::move(kf));
+        }
+    return 0;
 }
 
 // One frame of every running member, or false.  block: wait (in 1 ms slices, watching the quit flags) until they are all there;
@@ -647,6 +729,15 @@ int REBVO::BatchGroup::launch(long step, const std::vector<double> &ts) {
         }
         rc = edgehip_set_imu(hip, imu_in.data());
         if (rc != 0) return rc;
+    }
+    if (kf_track) {   // REBVO::saveKeyframes as the members' frames of this step carry it
+        int save = 0;
+        for (const Seat &st : seats) save |= st.running && st.cbuf && st.cbuf->save_kf;
+        if (save != kf_save) {
+            rc = edgehip_keyframe_set_save(hip, save);
+            if (rc != 0) return rc;
+            kf_save = save;
+        }
     }
     rc = edgehip_process_frame(hip, ts.data());
     if (rc != 0) return rc;
@@ -857,6 +948,7 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
     int rc = edgehip_read_nav_log(hip, (int)step, 1, navs.data());   // waits for this frame, not for the ones enqueued behind it
     if (rc == 0 && imu_mode) rc = edgehip_read_nav_imu_log(hip, (int)step, 1, navs_imu.data());
     if (rc == 0 && stereo) rc = edgehip_read_stereo_matches_log(hip, (int)step, 1, stereo_nm.data());
+    if (rc == 0 && kf_track) rc = kfDrain(-1, false);
     if (rc != 0) return rc;
     const double now = detail::now_s();
     tm.records += now - tr0;

@@ -173,6 +173,8 @@ void fill_nav_imu(const edgehip_nav_imu &n, PipeBuffer &pb) {
     is.init = n.init != 0;
 }
 }  // namespace detail
+
+void edgehipParams(const REBVOParameters &p, edgehip_params &out) { detail::fill_hip_params(p, out); }
 using detail::fill_hip_params;
 using detail::fill_nav;
 using detail::now_s;
@@ -273,7 +275,12 @@ REBVO::REBVO(const char *configFile)
     // accepted and ignored (subsystems that do not exist on this path)
     config.get("Camera", "Rotate180", p.rotatedCam, false);
     config.get("REBVO", "VideoNetEnabled", p.VideoNetEnabled, false);
-    config.get("REBVO", "TrackKeyFrames", p.TrackKeyFrames, false);
+    // src/rebvo/rebvo.cpp:153-157.  Upstream makes KFSavePercent mandatory beside TrackKeyFrames = 1; here a config without it keeps
+    // loading, as it did while the key was ignored: KFSavePercent stays 0, with which the criterion never holds (the first key frame only)
+    if (config.get("REBVO", "TrackKeyFrames", p.TrackKeyFrames, false) && p.TrackKeyFrames)
+        config.get("REBVO", "KFSavePercent", p.KFSavePercent, false);
+    else
+        p.TrackKeyFrames = false;
     if (config.get("REBVO", "StereoAvaiable", p.StereoAvaiable, false) && p.StereoAvaiable) {   // src/rebvo/rebvo.cpp:195-216
         InitOK &= config.get("DataSetCamera", "DataSetDirStereo", p.DataSetDirStereo);
         InitOK &= config.get("DataSetCamera", "DataSetFileStereo", p.DataSetFileStereo);
