@@ -884,6 +884,42 @@ int edgehip_download_keyframe_list_batch(edgehip_ctx *ctx, int n, const int32_t 
  * waited for.  EDGEHIP_ERR_ARG for an ordinal a list does not hold: nothing changes. */
 int edgehip_keyframe_list_restore(edgehip_ctx *ctx, int slot, const int32_t *ordinals /* [nseq] */);
 
+/* ---- key-frame covisibility (kfvo::countMatches, kfvo::kls_on_fov) ------------------------------------------------------------
+ * Which key frames of a sequence see the same edges: the candidate selection for loop closing, for re-localising against the list and
+ * for choosing the views of edgehip_surface_integrate.  For an ordered pair (to, from) every KeyLine of `from` is re-projected into
+ * `to` (keyframe::reProjectTo, include/mtracklib/keyframe.h:110-114; cam_model.h:146-169), looked up in the distance field
+ * global_tracker::build_field(to's edges, field_radius, field_min_mod) leaves (global_tracker.cpp:61-105; image.h:121-126), which is
+ * what keyframe::loadFromBinaryFile rebuilds (keyframe.cpp:119-123), and put to the tracker's match test
+ * (global_tracker::Calc_f_J_Complete<float>, global_tracker.cpp:115-165):
+ *     kl_on_fov, kl_match   kfvo::countMatches(kf_to, kf_from, kl_on_fov, kl_match, match_mod, match_ang, rho_tol, max_r)
+ *                           (src/mtracklib/kfvo.cpp:18-55), every integer the reference's
+ *     kls_on_fov            kfvo::kls_on_fov(kf_from, kf_to.Pose, kf_to.Pos) (kfvo.cpp:688-712)
+ *     guard                 `from` KeyLines whose re-projected image coordinate is not finite; the reference indexes its field out of
+ *                           bounds with them, here they are outside the image.  Non-zero: a precondition was broken (rho finite and
+ *                           non-zero, finite poses), as with edgehip_kf_track::guard.
+ * Read-only: no key frame, list entry or ring slot changes (countMatches also leaves the last pair's match in kf_from's m_id_f; that is
+ * not reproduced).  Scratch is allocated by the first call and freed with the key frames: nseq x min(M, 8) x w x h x 4 B of field planes
+ * and 52 B x max_points x nseq x (M + 1) of compact KeyLines. */
+typedef struct edgehip_kf_pair_count { int32_t kl_on_fov, kl_match, kls_on_fov, guard; } edgehip_kf_pair_count;
+typedef struct edgehip_kf_covis_args {
+    int32_t field_radius;          /* build_field's radius: SearchRange, the max_r the key-frame file stores */
+    float   field_min_mod;         /* <= 0: every KeyLine (the file loader's field) */
+    float   match_mod, match_ang, rho_tol, max_r;   /* countMatches' arguments */
+} edgehip_kf_covis_args;
+/* all ordered pairs of a sequence's key frames: positions 0..held-1 are the list's ordinals first..first+held-1, position held is the
+ * current key frame; M = capacity + 1 (1 without a list).  out[nseq][M][M], index [seq][to][from], diagonal included; pairs with a
+ * position the sequence does not have are all -1.  info[nseq] (may be NULL) is the edgehip_keyframe_list_info of the same moment.
+ * Synchronises.  EDGEHIP_ERR_STATE without key-frame tracking; EDGEHIP_ERR_ARG for NULL args or out, field_radius < 1 or > 4094 (the
+ * field's packed key has 12 bits for |t|) and max_points > 2^20 (20 bits for the KeyLine index); EDGEHIP_ERR_MEMORY when the scratch
+ * cannot be allocated: the context stays usable. */
+int edgehip_keyframe_covisibility(edgehip_ctx *ctx, const edgehip_kf_covis_args *args, edgehip_kf_pair_count *out, edgehip_kf_list_info *info);
+/* the query form: ring slot `slot`'s KeyLines as `from` (pose[nseq], or NULL for what edgehip_keyframe_insert takes by default)
+ * against every key frame of the same sequence as `to`: out[nseq][M]. */
+int edgehip_keyframe_covisibility_slot(edgehip_ctx *ctx, int slot, const edgehip_kf_pose *pose, const edgehip_kf_covis_args *args,
+                                       edgehip_kf_pair_count *out, edgehip_kf_list_info *info);
+/* Device time of the last of the two calls above, by HIP events: the field build (with the one read of the key frames) and the pair pass. */
+int edgehip_keyframe_covisibility_ms(edgehip_ctx *ctx, double *field_ms, double *pair_ms);
+
 /* ---- measurement ------------------------------------------------------------------------------------- */
 /* Names of the kernel groups timed by the built-in HIP-event profiler, and their accumulated device time.
  * edgehip_profile_enable(ctx, 1) brackets every launch group with events on the context stream (adds host

@@ -78,6 +78,10 @@ struct edgehip_ctx::KfTrack {
     edgehip::KfListDev list = {};
     void *list_arena = nullptr;       // records | headers | per-sequence state | restore requests
     int32_t *list_req_dev = nullptr, *list_req_host = nullptr;      // [nseq] edgehip_keyframe_list_restore's ring positions
+    // keyframe_covis.hip's scratch: allocated by the first call, for covis_m = list capacity + 1 positions per sequence
+    void *covis_arena = nullptr;
+    int covis_m = 0;
+    double covis_ms[2] = {0, 0};      // the last call's device time: field build (with the gather), pair pass
 };
 
 namespace edgehip {
@@ -88,5 +92,6 @@ int kf_list_reset_enqueue(edgehip_ctx *c);           // edgehip_reset: no entrie
 int kf_list_retire_enqueue(edgehip_ctx *c);
 // edgehip_upload_keyframe: posts the retirement of sequence `seq`'s key frame (if it has one) and enqueues its records (no-op when off).
 int kf_list_retire_one_enqueue(edgehip_ctx *c, int seq);
+void kf_covis_free(edgehip_ctx *c);                  // keyframe_covis.hip's scratch; behind a synchronisation of c->stream; no-op when absent
 
 }  // namespace edgehip

@@ -240,6 +240,21 @@ class KfListInfo(C.Structure):
 KF_POSE_DTYPE = np.dtype(KfPose)
 KF_TRACK_DTYPE = np.dtype(KfTrack)
 KF_LIST_INFO_DTYPE = np.dtype(KfListInfo)
+
+
+class KfPairCount(C.Structure):
+    """edgehip_kf_pair_count: countMatches' two counts, kls_on_fov's, and the KeyLines whose projection was not finite."""
+    _fields_ = [("kl_on_fov", C.c_int32), ("kl_match", C.c_int32), ("kls_on_fov", C.c_int32), ("guard", C.c_int32)]
+
+
+class KfCovisArgs(C.Structure):
+    """edgehip_kf_covis_args: build_field's (radius, min_mod) and countMatches' (match_mod, match_ang, rho_tol, max_r)."""
+    _fields_ = [("field_radius", C.c_int32), ("field_min_mod", C.c_float), ("match_mod", C.c_float), ("match_ang", C.c_float),
+                ("rho_tol", C.c_float), ("max_r", C.c_float)]
+
+
+KF_PAIR_COUNT_DTYPE = np.dtype(KfPairCount)
+assert KF_PAIR_COUNT_DTYPE.itemsize == 16 and C.sizeof(KfCovisArgs) == 24
 NAV_DTYPE = np.dtype(Nav)   # numpy view of edgehip_nav (same offsets as the ctypes struct)
 assert NAV_DTYPE.itemsize == C.sizeof(Nav)
 
@@ -275,6 +290,7 @@ EXPORTS = [
     "edgehip_keyframe_back_correct", "edgehip_read_keyframe_track", "edgehip_download_keyframe", "edgehip_upload_keyframe",
     "edgehip_keyframe_set_save", "edgehip_keyframe_list_enable", "edgehip_keyframe_list_info", "edgehip_download_keyframe_list",
     "edgehip_download_keyframe_list_batch", "edgehip_keyframe_list_restore",
+    "edgehip_keyframe_covisibility", "edgehip_keyframe_covisibility_slot", "edgehip_keyframe_covisibility_ms",
 ]
 
 _lib = None
@@ -1111,6 +1127,7 @@ class EdgeHip:
         in_frame_driver=False keeps the store for the stage-level calls below and leaves process_frame as it is without the feature."""
         mode = 0 if not enable else (1 if in_frame_driver else 2)
         self._ck(self.lib.edgehip_keyframe_track_enable(self.ctx, mode, C.c_double(kf_save_percent), int(bool(save_keyframes))))
+        self._kf_list_capacity = 0   # (the call frees the list with the key frames)
 
     @staticmethod
     def kf_pose(Pose=None, Pos=None, t=0.0, K=1.0):
@@ -1181,6 +1198,7 @@ class EdgeHip:
     def keyframe_list_enable(self, capacity):
         """A ring of `capacity` retired key frames per sequence (0 frees it); needs keyframe_track_enable."""
         self._ck(self.lib.edgehip_keyframe_list_enable(self.ctx, int(capacity)))
+        self._kf_list_capacity = int(capacity)
 
     def keyframe_list_info(self):
         """-> structured array [nseq] (KF_LIST_INFO_DTYPE): kf_count, first, held, overwritten."""
@@ -1212,6 +1230,40 @@ class EdgeHip:
         """List entry ordinals[seq] of every sequence back into ring slot `slot` (-1: leave that sequence's slot alone)."""
         o = np.ascontiguousarray(np.broadcast_to(np.asarray(ordinals, np.int32), (self.nseq,))).copy()
         self._ck(self.lib.edgehip_keyframe_list_restore(self.ctx, slot, o.ctypes.data_as(C.c_void_p)))
+
+    # ---- key-frame covisibility (kfvo::countMatches, kfvo::kls_on_fov) ----
+    @staticmethod
+    def _covis_args(field_radius, field_min_mod, match_mod, match_ang, rho_tol, max_r):
+        return KfCovisArgs(int(field_radius), float(field_min_mod), float(match_mod), float(match_ang), float(rho_tol), float(max_r))
+
+    def keyframe_covisibility(self, field_radius, match_mod, match_ang, rho_tol, max_r, field_min_mod=0.0):
+        """Every ordered pair of each sequence's key frames (list entries oldest first, then the current one) -> (counts, info):
+        counts a structured array (nseq, M, M) of KF_PAIR_COUNT_DTYPE indexed [seq][to][from], M = list capacity + 1, -1 where the
+        sequence lacks a position; info as keyframe_list_info() returns it, of the same moment."""
+        m = getattr(self, "_kf_list_capacity", 0) + 1
+        out = np.zeros((self.nseq, m, m), KF_PAIR_COUNT_DTYPE)
+        info = np.zeros(self.nseq, KF_LIST_INFO_DTYPE)
+        a = self._covis_args(field_radius, field_min_mod, match_mod, match_ang, rho_tol, max_r)
+        self._ck(self.lib.edgehip_keyframe_covisibility(self.ctx, C.byref(a), out.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p)))
+        return out, info
+
+    def keyframe_covisibility_slot(self, slot, field_radius, match_mod, match_ang, rho_tol, max_r, field_min_mod=0.0, poses=None):
+        """Ring slot `slot`'s KeyLines as `from` (poses: one KfPose per sequence, or None for the newest nav record and seq_state.K)
+        against every key frame of the same sequence -> (counts (nseq, M), info)."""
+        m = getattr(self, "_kf_list_capacity", 0) + 1
+        out = np.zeros((self.nseq, m), KF_PAIR_COUNT_DTYPE)
+        info = np.zeros(self.nseq, KF_LIST_INFO_DTYPE)
+        a = self._covis_args(field_radius, field_min_mod, match_mod, match_ang, rho_tol, max_r)
+        arr = None if poses is None else (KfPose * self.nseq)(*poses)
+        self._ck(self.lib.edgehip_keyframe_covisibility_slot(self.ctx, int(slot), arr, C.byref(a), out.ctypes.data_as(C.c_void_p),
+                                                             info.ctypes.data_as(C.c_void_p)))
+        return out, info
+
+    def keyframe_covisibility_ms(self):
+        """-> (field build ms, pair pass ms) of the last covisibility call, by HIP events."""
+        f, p = C.c_double(0), C.c_double(0)
+        self._ck(self.lib.edgehip_keyframe_covisibility_ms(self.ctx, C.byref(f), C.byref(p)))
+        return f.value, p.value
 
     def download_plane(self, seq, which):
         idx = {"img0": 0, "img1": 1, "dog": 2, "dx": 3, "dy": 4}[which]

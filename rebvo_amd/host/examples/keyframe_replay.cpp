@@ -3,7 +3,7 @@
 // REBVO::kf_list goes into a key-frame file the reference's kf_visualizer loads.  Used by tests/test_keyframe_host_gpu.py.
 //
 //   keyframe_replay <GlobalConfig> <frames.rgb24> <objects> <frames_per_object> <t0> <dt> <out_prefix>
-//                   [--group NAME] [--start F] [--end F] [--disagree] [--map]
+//                   [--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis]
 //
 // frames.rgb24 = objects x frames_per_object x ImageHeight x ImageWidth x 3 bytes: object i's frame k is frame i * frames_per_object + k
 // and carries the stamp t0 + k dt.  --group puts all objects into one batch group of that name (without it every object has its own
@@ -13,6 +13,8 @@
 // --map: what app/kf_visualizer/main.cpp:84-116 does with object 0's list, through the C ABI of the device library: every key frame's
 // KeyLines into a ring slot (edgehip_upload_keylines), edgehip_depth_fill, edgehip_surface_view_capture with its pose; then
 // edgehip_surface_space, edgehip_surface_integrate and the visibility download.  Prints "view <j>: <hidden> of <cells> cells hidden".
+// --covis: after the last frame's record and before CleanUp(), REBVO::keyframeCovisibility of every object with (SearchRange, 0,
+// MatchThreshModule, MatchThreshAngle in radians, 3, SearchRange).  Prints "covis <i> m <m>:" and the m x m x 4 counts, [to][from].
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -76,7 +78,7 @@ static int map_views(const REBVOParameters &prm, std::vector<keyframe> &list) {
 int main(int argn, char **argv) {
     if (argn < 8) {
         std::cout << "usage: keyframe_replay <GlobalConfig> <frames.rgb24> <objects> <frames_per_object> <t0> <dt> <out_prefix> "
-                     "[--group NAME] [--start F] [--end F] [--disagree] [--map]\n";
+                     "[--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis]\n";
         return 2;
     }
     const int N = atoi(argv[3]), K = atoi(argv[4]);
@@ -84,7 +86,7 @@ int main(int argn, char **argv) {
     const std::string prefix = argv[7];
     std::string group;
     int start = -1, end = -1;
-    bool disagree = false, map = false;
+    bool disagree = false, map = false, covis = false;
     for (int a = 8; a < argn; a++) {
         const std::string s = argv[a];
         if (s == "--group" && a + 1 < argn) group = argv[++a];
@@ -92,6 +94,7 @@ int main(int argn, char **argv) {
         else if (s == "--end" && a + 1 < argn) end = atoi(argv[++a]);
         else if (s == "--disagree") disagree = true;
         else if (s == "--map") map = true;
+        else if (s == "--covis") covis = true;
         else { std::cout << "unknown argument " << s << "\n"; return 2; }
     }
     if (N < 1 || K < 2) { std::cout << "bad counts\n"; return 2; }
@@ -139,6 +142,18 @@ int main(int argn, char **argv) {
             if (!obj[i]->Running() || std::chrono::steady_clock::now() > deadline) { bad = true; break; }
             std::this_thread::sleep_for(std::chrono::microseconds(100));
         }
+    for (int i = 0; i < N && covis && !bad; i++) {
+        KfCovisArgs ca;
+        ca.field_radius = (int)prm.SearchRange; ca.field_min_mod = 0.f;
+        ca.match_mod = (float)prm.MatchThreshModule; ca.match_ang = (float)(prm.MatchThreshAngle * M_PI / 180.0);
+        ca.rho_tol = 3.f; ca.max_r = (float)prm.SearchRange;
+        std::vector<KfPairCount> rows;
+        int m = 0;
+        if (!obj[i]->keyframeCovisibility(ca, rows, m)) { std::cout << "covis " << i << ": refused\n"; continue; }
+        std::cout << "covis " << i << " m " << m << ":";
+        for (const KfPairCount &c : rows) std::cout << " " << c.kl_on_fov << " " << c.kl_match << " " << c.kls_on_fov << " " << c.guard;
+        std::cout << "\n";
+    }
     for (int i = 0; i < N; i++) obj[i]->CleanUp();
     if (bad) { std::cout << "an object stopped early: " << obj[0]->lastError() << "\n"; return 6; }
     for (int i = 0; i < N; i++) {

@@ -66,6 +66,14 @@ struct edgehip_ctx;
 struct edgehip_params;
 
 namespace rebvo {
+// (mirror only) REBVO::keyframeCovisibility's arguments and counts: edgehip_kf_covis_args / edgehip_kf_pair_count of include/edgehip.h,
+// field for field — build_field's (radius, min_mod) and countMatches' (match_mod, match_ang, rho_tol, max_r); countMatches' two counts,
+// kls_on_fov's, and the KeyLines whose re-projection was not finite.
+struct KfCovisArgs { int32_t field_radius; float field_min_mod, match_mod, match_ang, rho_tol, max_r; };
+struct KfPairCount { int32_t kl_on_fov, kl_match, kls_on_fov, guard; };
+}
+
+namespace rebvo {
 
 class DataSetCam;
 
@@ -518,6 +526,15 @@ public:
     // objects ignore the key and the list stays empty).  Retired key frames arrive as the steps that replaced them complete; CleanUp()
     // appends the current one.  As upstream, reading it while the object runs is unsynchronised.
     std::vector<keyframe> kf_list;
+    // (mirror only) Which of this object's key frames see the same edges: kfvo::countMatches (src/mtracklib/kfvo.cpp:18-55) and
+    // kfvo::kls_on_fov (kfvo.cpp:688-712) of every ordered pair, on the device (edgehip_keyframe_covisibility, include/edgehip.h), for an
+    // object on the group engine with TrackKeyFrames = 1 between Init() and CleanUp().  The key frames are the ones the device holds for
+    // this object at that moment: the newest retired ones — the tail of kf_list, at most 4 — oldest first, then the current key frame
+    // (which kf_list receives at CleanUp()).  out[to * m + from], m positions per side, every count -1 for a position the object does
+    // not have.  The group's thread makes the call between two steps (it is the one thread that talks to the context) and scores every
+    // member's pairs on the way; false when the object has no group, tracks no key frames or has stopped, or when the device refuses the
+    // arguments.
+    bool keyframeCovisibility(const KfCovisArgs &args, std::vector<KfPairCount> &out, int &m);
     // frame-by-frame mode: no new frame is taken from the camera until advanceFrameByFrame() (rebvo.h:481-488, rebvo_first_t.cpp:154-159)
     bool toggleFrameByFrame() { return frame_by_frame = !frame_by_frame; }
     bool advanceFrameByFrame() { return frame_by_frame_advance = true; }

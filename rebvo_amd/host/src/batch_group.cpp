@@ -42,6 +42,7 @@
 #include <cstring>
 #include <iostream>
 #include <map>
+#include <atomic>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -175,6 +176,15 @@ public:
     int kf_save = 0;               // the context's save flag (edgehip_keyframe_set_save)
     std::vector<int32_t> kf_next;  // [cap] the next ordinal to move into the member's kf_list
     int kfDrain(int only_seat, bool with_current);   // only_seat < 0: every running member; with_current: the current key frame too (CleanUp)
+    // REBVO::keyframeCovisibility: a member's request waits under `mut` for the group's thread, which serves it at the head of a gather pass
+    // (every step, and every millisecond while the members have no frames) and refuses what is left when it ends
+    static_assert(sizeof(KfCovisArgs) == sizeof(edgehip_kf_covis_args) && sizeof(KfPairCount) == sizeof(edgehip_kf_pair_count), "the mirror's structs are the C ABI's");
+    struct CovisReq { int seat = -1; edgehip_kf_covis_args args; std::vector<KfPairCount> *out = nullptr; int *m = nullptr; bool done = false, ok = false; };
+    std::vector<CovisReq *> covis_reqs;
+    std::atomic<int> covis_waiting{0};
+    bool thread_done = false;
+    void serveCovis();
+    void refuseCovis();
     int cb_depth = 2;              // steps in flight when somebody has a callback (REBVO_GROUP_CB_DEPTH=1: the round-5 behaviour, A/B)
 
     void threadMain();
@@ -604,12 +614,61 @@ int REBVO::BatchGroup::kfDrain(int only_seat, bool with_current) {
     return 0;
 }
 
+void REBVO::BatchGroup::serveCovis() {
+    if (!covis_waiting.load(std::memory_order_acquire)) return;
+    std::vector<CovisReq *> take;
+    {
+        std::lock_guard<std::mutex> lk(mut);
+        take.swap(covis_reqs);
+        covis_waiting.store(0, std::memory_order_release);
+    }
+    const size_t M = kKfListCapacity + 1;
+    std::vector<edgehip_kf_pair_count> all((size_t)cap * M * M);
+    for (CovisReq *r : take) {
+        const bool ok = kf_track && edgehip_keyframe_covisibility(hip, &r->args, all.data(), nullptr) == 0;
+        if (ok) {
+            r->out->resize(M * M);
+            std::memcpy(r->out->data(), all.data() + (size_t)r->seat * M * M, sizeof(KfPairCount) * M * M);
+            *r->m = (int)M;
+        }
+        std::lock_guard<std::mutex> lk(mut);
+        r->ok = ok;
+        r->done = true;
+    }
+    cv.notify_all();
+}
+
+void REBVO::BatchGroup::refuseCovis() {
+    {
+        std::lock_guard<std::mutex> lk(mut);
+        thread_done = true;
+        for (CovisReq *r : covis_reqs) r->done = true;
+        covis_reqs.clear();
+    }
+    cv.notify_all();
+}
+
+bool REBVO::keyframeCovisibility(const KfCovisArgs &args, std::vector<KfPairCount> &out, int &m) {
+    BatchGroup *g = group;
+    if (!g || group_seat < 0 || quit) return false;
+    BatchGroup::CovisReq r;
+    r.seat = group_seat; r.out = &out; r.m = &m;
+    std::memcpy(&r.args, &args, sizeof r.args);
+    std::unique_lock<std::mutex> lk(g->mut);
+    if (!g->started || g->thread_done || g->failed || !g->kf_track || !g->seats[group_seat].running) return false;
+    g->covis_reqs.push_back(&r);
+    g->covis_waiting.store(1, std::memory_order_release);
+    g->cv.wait(lk, [&] { return r.done; });
+    return r.ok;
+}
+
 // One frame of every running member, or false.  block: wait (in 1 ms slices, watching the quit flags) until they are all there;
 // otherwise a single pass.  A member whose quit flag is up is marked `leaving` and the call returns at once: the caller finishes
 // the step in flight — that member's last submitted frame may be in it, and a frame that was taken from the ring is tracked to
 // the end, as in the reference, where CleanUp() joins a thread that is never interrupted inside a frame — and closes the seat.
 bool REBVO::BatchGroup::gather(bool block, bool &any_running, bool &any_leaving) {
     while (true) {
+        serveCovis();
         bool all = true, waited = false;   // a blocking pass waits (1 ms at most) on the FIRST member whose frame is missing and only looks at the
                                            // others: a pass never takes longer than that, however many members there are (the quit flags
                                            // are read at the head of every pass — a thousand 1 ms waits in a row made CleanUp() of a
@@ -1221,6 +1280,7 @@ void REBVO::BatchGroup::threadMain() {
         error = edgehip_last_error();
     }
     if (rc != 0) (void)edgehip_sync(hip);
+    refuseCovis();
     dropExports();
     for (Seat &st : seats)
         if (st.running) closeSeat(st);
