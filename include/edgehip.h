@@ -920,6 +920,51 @@ int edgehip_keyframe_covisibility_slot(edgehip_ctx *ctx, int slot, const edgehip
 /* Device time of the last of the two calls above, by HIP events: the field build (with the one read of the key frames) and the pair pass. */
 int edgehip_keyframe_covisibility_ms(edgehip_ctx *ctx, double *field_ms, double *pair_ms);
 
+/* ---- key-frame relative-pose constraint (kfvo::OptimizeRelContraint) ------------------------------------------------------------
+ * The metric use of the links the tracking above maintains: from the key frame's m_id_f (direction 0) or the frame list's m_id_kf
+ * (direction 1) alone, with no distance field, kfvo::OptimizeRelContraint (src/mtracklib/kfvo.cpp:527-604; its evaluation
+ * OptimizeRelConstraint1Iter, :344-420) makes a 6-DoF relative pose X = [BRelPos, ln(BRelRot)], its information matrix W_X = JtJ, its
+ * covariance R_X = Cholesky<6>(JtJ).get_inverse() and, for direction 1, the scale ratio of optimizeScaleF2KF (:263-302) with its weight:
+ * the fields relPosPose, WrelPosPose, K, WK of the OdometryMeas the reference's pose_graph keeps per key frame
+ * (include/mtracklib/pose_graph.h:31-47).  Upstream defines the function and never calls it.  Every sequence's current key frame is
+ * constrained against ring slot slot_new in one call; all arithmetic is fp64 in the reference's order per KeyLine, the sums over
+ * KeyLines run in a fixed order of the device's own (tests/keyframe_constraint_port.py restates the rules).
+ *     direction 1   walks the slot's KeyLines, partner = key frame's KeyLine m_id_kf; start pose BRelRot = kf.Pose^T * Pose,
+ *                   BRelPos = kf.Pose^T * (Pos - kf.Pos) / K (:538-541)
+ *     direction 0   walks the key frame's KeyLines, partner = the slot's KeyLine m_id_f; BRelRot = Pose^T * kf.Pose,
+ *                   BRelPos = Pose^T * (kf.Pos - Pos) / kf.K (:542-544)
+ * The reference has no defined result for a sequence without links (it aborts in SO3::coerce) or with a NaN on a linked KeyLine; here
+ *     guard bit 0   the sequence stopped stepping at a non-finite dX or JtJ; X is the last accepted pose (the start pose if none)
+ *     guard bit 1   the last evaluation counted fewer than 6 links (the reference's arithmetic still runs; the result means nothing)
+ *     guard bit 2   a link outside the list it indexes was taken as unmatched (the reference reads out of bounds)
+ * and none of them stops the other sequences of the batch.  A sequence without a key frame has no links. */
+typedef struct edgehip_kf_constraint_args { int32_t direction, iter_max; double k_huber; } edgehip_kf_constraint_args;
+typedef struct edgehip_kf_constraint {
+    double X[6], W_X[36], R_X[36];
+    double ratio, E, E0;          /* E/E0 (the return value), and both terms */
+    double Kp, W_Kp;              /* optimizeScaleF2KF; 0, 0 for direction 0 */
+    int32_t links, inliers;       /* match_num of the LAST evaluation */
+    int32_t evals, accepted, guard, pad;
+} edgehip_kf_constraint;
+/* Pose[nseq][9], Pos[nseq][3], K[nseq], or all three NULL for what edgehip_keyframe_forward_correct takes by default and
+ * edgehip_seq_state::K.  out[nseq].  Read-only on the key frames and the slot.  Synchronises.  EDGEHIP_ERR_STATE without key-frame
+ * tracking; EDGEHIP_ERR_ARG for NULL args or out, iter_max < 0, a direction that is not 0 or 1, a slot out of range, or some but not
+ * all of Pose, Pos, K; EDGEHIP_ERR_MEMORY when the scratch (92 B x max_points x nseq, allocated by the first call and freed with the
+ * key frames) cannot be allocated: the context stays usable. */
+int edgehip_keyframe_constraint(edgehip_ctx *ctx, int slot_new, const double *Pose, const double *Pos, const double *K,
+                                const edgehip_kf_constraint_args *args, edgehip_kf_constraint *out);
+/* kfvo::mutualExclusionSimple(kf, slot_new, dist_t, discard_non_mutual, kf_to_frame) (kfvo.cpp:423-522): the pruning pass in front of
+ * the constraint.  kf_to_frame = 1 edits the key frame's m_id_f (a link whose partner does not link back is dropped when
+ * discard_non_mutual; one whose partner links back to a KeyLine further than dist_t away, by the Euclidean distance of the float p_m,
+ * is dropped), kf_to_frame = 0 the slot's m_id_kf (the distance is |difference . u_m| in float); nothing else changes.  In-stream like
+ * the correct steps; counts[nseq][2] (may be NULL: no synchronisation) = (links seen, links kept).  A link outside the list it indexes
+ * is left alone and not counted; a back link outside the walked list is seen, not kept, and left alone (the reference reads out of
+ * bounds in both cases).  EDGEHIP_ERR_STATE and EDGEHIP_ERR_ARG for the slot as above; the call allocates nothing (its counts live
+ * with the key frames). */
+int edgehip_keyframe_mutual_exclusion(edgehip_ctx *ctx, int slot_new, double dist_t, int discard_non_mutual, int kf_to_frame, int32_t *counts);
+/* Device time of the last edgehip_keyframe_constraint, by HIP events: the link gather and the solve. */
+int edgehip_keyframe_constraint_ms(edgehip_ctx *ctx, double *gather_ms, double *solve_ms);
+
 /* ---- measurement ------------------------------------------------------------------------------------- */
 /* Names of the kernel groups timed by the built-in HIP-event profiler, and their accumulated device time.
  * edgehip_profile_enable(ctx, 1) brackets every launch group with events on the context stream (adds host

@@ -82,6 +82,10 @@ struct edgehip_ctx::KfTrack {
     void *covis_arena = nullptr;
     int covis_m = 0;
     double covis_ms[2] = {0, 0};      // the last call's device time: field build (with the gather), pair pass
+    // keyframe_constraint.hip's scratch: the rows, allocated by the first edgehip_keyframe_constraint (92 B per KeyLine of capacity and sequence)
+    void *kc_arena = nullptr;
+    int32_t *kc_counts = nullptr;     // [nseq][2] edgehip_keyframe_mutual_exclusion's (links seen, links kept); allocated with the key frames
+    double kc_ms[2] = {0, 0};         // the last constraint call's device time: gather, solve
 };
 
 namespace edgehip {
@@ -92,6 +96,10 @@ int kf_list_reset_enqueue(edgehip_ctx *c);           // edgehip_reset: no entrie
 int kf_list_retire_enqueue(edgehip_ctx *c);
 // edgehip_upload_keyframe: posts the retirement of sequence `seq`'s key frame (if it has one) and enqueues its records (no-op when off).
 int kf_list_retire_one_enqueue(edgehip_ctx *c, int seq);
+// What every stage-level entry point that reads ring slot `slot` does first: EDGEHIP_ERR_STATE without key-frame tracking, EDGEHIP_ERR_ARG
+// for a slot out of range, then the slot's KeyLines as edgehip_download_keylines returns them, ordered behind stage A.
+int kf_entry(edgehip_ctx *c, int slot, const char *who);
 void kf_covis_free(edgehip_ctx *c);                  // keyframe_covis.hip's scratch; behind a synchronisation of c->stream; no-op when absent
+void kf_constraint_free(edgehip_ctx *c);             // keyframe_constraint.hip's scratch; the same
 
 }  // namespace edgehip

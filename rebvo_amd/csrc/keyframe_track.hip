@@ -447,6 +447,7 @@ void edgehip::kf_track_free(edgehip_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     kf_list_free(c);
     kf_covis_free(c);
+    kf_constraint_free(c);
     for (void *q : d->dev) (void)hipFree(q);
     if (d->pose12_host) (void)hipHostFree(d->pose12_host);
     if (d->blk_host) (void)hipHostFree(d->blk_host);
@@ -497,7 +498,8 @@ int edgehip_keyframe_track_enable(edgehip_ctx *c, int enable, double kf_save_per
     if (stereo) { field(&KlSoA::stereo_m_id); field(&KlSoA::stereo_rho); field(&KlSoA::stereo_s_rho); }
     ok = ok && kf_alloc(d, &d->kl_dev, B) && kf_alloc(d, &d->ks, B) && kf_alloc(d, &d->rec, B) && kf_alloc(d, &d->table, B * CAP) &&
          kf_alloc(d, &d->dist, B * CAP) && kf_alloc(d, &d->keys, B * (size_t)d->np2cap) && kf_alloc(d, &d->aos, CAP) &&
-         kf_alloc(d, &d->pose12_dev, B * 12) && kf_alloc(d, &d->blk_dev, B) && kf_alloc(d, &d->mask_dev, B);
+         kf_alloc(d, &d->pose12_dev, B * 12) && kf_alloc(d, &d->blk_dev, B) && kf_alloc(d, &d->mask_dev, B) &&
+         kf_alloc(d, &d->kc_counts, B * 2);
     ok = ok && hipHostMalloc((void **)&d->pose12_host, 8 * 12 * B, hipHostMallocDefault) == hipSuccess &&
          hipHostMalloc((void **)&d->blk_host, sizeof(edgehip_kf_pose) * B, hipHostMallocDefault) == hipSuccess &&
          hipHostMalloc((void **)&d->mask_host, B, hipHostMallocDefault) == hipSuccess &&
@@ -614,7 +616,7 @@ int edgehip::kf_frame_end_enqueue(edgehip_ctx *c, int slot_new) {   // :591-596
 }
 
 // ---- stage-level entry points ---------------------------------------------------------------------------------------------------------
-static int kf_entry(edgehip_ctx *c, int slot, const char *who) {
+int edgehip::kf_entry(edgehip_ctx *c, int slot, const char *who) {
     if (!c->kftrack) { set_error(std::string(who) + ": key-frame tracking is not enabled (edgehip_keyframe_track_enable)"); return EDGEHIP_ERR_STATE; }
     if (slot < 0 || slot >= c->plan.nslots) { set_error(std::string(who) + ": slot out of range"); return EDGEHIP_ERR_ARG; }
     if (int e = rot_materialize_enqueue(c, slot)) return e;   // the slot's KeyLines as edgehip_download_keylines returns them

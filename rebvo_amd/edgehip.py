@@ -255,6 +255,24 @@ class KfCovisArgs(C.Structure):
 
 KF_PAIR_COUNT_DTYPE = np.dtype(KfPairCount)
 assert KF_PAIR_COUNT_DTYPE.itemsize == 16 and C.sizeof(KfCovisArgs) == 24
+
+
+class KfConstraintArgs(C.Structure):
+    """edgehip_kf_constraint_args: OptimizeRelContraint's etracket_2_keyframe, iter_max and k_huber."""
+    _fields_ = [("direction", C.c_int32), ("iter_max", C.c_int32), ("k_huber", C.c_double)]
+
+
+class KfConstraint(C.Structure):
+    """edgehip_kf_constraint: X, W_X, R_X, E/E0 with both terms, optimizeScaleF2KF's pair, match_num of the last evaluation, and the
+    evaluations run, steps accepted and guard bits."""
+    _fields_ = [("X", C.c_double * 6), ("W_X", C.c_double * 36), ("R_X", C.c_double * 36),
+                ("ratio", C.c_double), ("E", C.c_double), ("E0", C.c_double), ("Kp", C.c_double), ("W_Kp", C.c_double),
+                ("links", C.c_int32), ("inliers", C.c_int32), ("evals", C.c_int32), ("accepted", C.c_int32), ("guard", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+KF_CONSTRAINT_DTYPE = np.dtype(KfConstraint)
+assert KF_CONSTRAINT_DTYPE.itemsize == 688 and C.sizeof(KfConstraintArgs) == 16
 NAV_DTYPE = np.dtype(Nav)   # numpy view of edgehip_nav (same offsets as the ctypes struct)
 assert NAV_DTYPE.itemsize == C.sizeof(Nav)
 
@@ -291,6 +309,7 @@ EXPORTS = [
     "edgehip_keyframe_set_save", "edgehip_keyframe_list_enable", "edgehip_keyframe_list_info", "edgehip_download_keyframe_list",
     "edgehip_download_keyframe_list_batch", "edgehip_keyframe_list_restore",
     "edgehip_keyframe_covisibility", "edgehip_keyframe_covisibility_slot", "edgehip_keyframe_covisibility_ms",
+    "edgehip_keyframe_constraint", "edgehip_keyframe_mutual_exclusion", "edgehip_keyframe_constraint_ms",
 ]
 
 _lib = None
@@ -1264,6 +1283,40 @@ class EdgeHip:
         f, p = C.c_double(0), C.c_double(0)
         self._ck(self.lib.edgehip_keyframe_covisibility_ms(self.ctx, C.byref(f), C.byref(p)))
         return f.value, p.value
+
+    # ---- key-frame relative-pose constraint (kfvo::OptimizeRelContraint, mutualExclusionSimple) ----
+    def keyframe_constraint(self, slot_new, direction, iter_max, k_huber, Pose=None, Pos=None, K=None):
+        """Every sequence's current key frame against ring slot `slot_new` -> a dict of arrays: X (nseq, 6), W_X and R_X (nseq, 6, 6),
+        ratio, E, E0, Kp, W_Kp (nseq,), links, inliers, evals, accepted, guard (nseq,) int32.  Pose (nseq, 3, 3), Pos (nseq, 3) and
+        K (nseq,) are given together, or all None for Pose*R, Pos - Pose*R*V*K and K from seq_state."""
+        out = np.zeros(self.nseq, KF_CONSTRAINT_DTYPE)
+        a = KfConstraintArgs(int(direction), int(iter_max), float(k_huber))
+        pp = pt = pk = None
+        if Pose is not None or Pos is not None or K is not None:
+            assert Pose is not None and Pos is not None and K is not None, "Pose, Pos and K are given together"
+            P = np.ascontiguousarray(np.broadcast_to(np.asarray(Pose, np.float64).reshape(-1, 9), (self.nseq, 9)))
+            T = np.ascontiguousarray(np.broadcast_to(np.asarray(Pos, np.float64).reshape(-1, 3), (self.nseq, 3)))
+            S = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1), (self.nseq,)))
+            pp, pt, pk = _dp(P), _dp(T), _dp(S)
+        self._ck(self.lib.edgehip_keyframe_constraint(self.ctx, int(slot_new), pp, pt, pk, C.byref(a), out.ctypes.data_as(C.c_void_p)))
+        res = {k: out[k].copy() for k in out.dtype.names if k != "pad"}
+        res["W_X"] = res["W_X"].reshape(self.nseq, 6, 6)
+        res["R_X"] = res["R_X"].reshape(self.nseq, 6, 6)
+        return res
+
+    def keyframe_mutual_exclusion(self, slot_new, dist_t, discard_non_mutual, kf_to_frame, want_counts=True):
+        """mutualExclusionSimple between the key frames and `slot_new`: kf_to_frame edits the key frames' m_id_f, otherwise the slot's
+        m_id_kf -> counts (nseq, 2) = (links seen, links kept), or None (and no synchronisation) when want_counts is False."""
+        cnt = np.zeros((self.nseq, 2), np.int32) if want_counts else None
+        self._ck(self.lib.edgehip_keyframe_mutual_exclusion(self.ctx, int(slot_new), C.c_double(dist_t), int(bool(discard_non_mutual)),
+                                                            int(bool(kf_to_frame)), None if cnt is None else cnt.ctypes.data_as(C.c_void_p)))
+        return cnt
+
+    def keyframe_constraint_ms(self):
+        """-> (gather ms, solve ms) of the last keyframe_constraint call, by HIP events."""
+        g, s = C.c_double(0), C.c_double(0)
+        self._ck(self.lib.edgehip_keyframe_constraint_ms(self.ctx, C.byref(g), C.byref(s)))
+        return g.value, s.value
 
     def download_plane(self, seq, which):
         idx = {"img0": 0, "img1": 1, "dog": 2, "dx": 3, "dy": 4}[which]

@@ -3,7 +3,7 @@
 // REBVO::kf_list goes into a key-frame file the reference's kf_visualizer loads.  Used by tests/test_keyframe_host_gpu.py.
 //
 //   keyframe_replay <GlobalConfig> <frames.rgb24> <objects> <frames_per_object> <t0> <dt> <out_prefix>
-//                   [--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis]
+//                   [--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis] [--constraint]
 //
 // frames.rgb24 = objects x frames_per_object x ImageHeight x ImageWidth x 3 bytes: object i's frame k is frame i * frames_per_object + k
 // and carries the stamp t0 + k dt.  --group puts all objects into one batch group of that name (without it every object has its own
@@ -15,6 +15,9 @@
 // edgehip_surface_space, edgehip_surface_integrate and the visibility download.  Prints "view <j>: <hidden> of <cells> cells hidden".
 // --covis: after the last frame's record and before CleanUp(), REBVO::keyframeCovisibility of every object with (SearchRange, 0,
 // MatchThreshModule, MatchThreshAngle in radians, 3, SearchRange).  Prints "covis <i> m <m>:" and the m x m x 4 counts, [to][from].
+// --constraint: at the same point, REBVO::keyframeConstraint of every object in both directions with (iter_max, k_huber) = (10, 2): the
+// current key frame against the newest frame.  Prints "constraint <i> dir <d>:" and X[6], ratio, E, E0, Kp, W_Kp with 17 significant
+// digits, then links, inliers, evals, accepted, guard.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -78,7 +81,7 @@ static int map_views(const REBVOParameters &prm, std::vector<keyframe> &list) {
 int main(int argn, char **argv) {
     if (argn < 8) {
         std::cout << "usage: keyframe_replay <GlobalConfig> <frames.rgb24> <objects> <frames_per_object> <t0> <dt> <out_prefix> "
-                     "[--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis]\n";
+                     "[--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis] [--constraint]\n";
         return 2;
     }
     const int N = atoi(argv[3]), K = atoi(argv[4]);
@@ -86,7 +89,7 @@ int main(int argn, char **argv) {
     const std::string prefix = argv[7];
     std::string group;
     int start = -1, end = -1;
-    bool disagree = false, map = false, covis = false;
+    bool disagree = false, map = false, covis = false, constraint = false;
     for (int a = 8; a < argn; a++) {
         const std::string s = argv[a];
         if (s == "--group" && a + 1 < argn) group = argv[++a];
@@ -95,6 +98,7 @@ int main(int argn, char **argv) {
         else if (s == "--disagree") disagree = true;
         else if (s == "--map") map = true;
         else if (s == "--covis") covis = true;
+        else if (s == "--constraint") constraint = true;
         else { std::cout << "unknown argument " << s << "\n"; return 2; }
     }
     if (N < 1 || K < 2) { std::cout << "bad counts\n"; return 2; }
@@ -154,6 +158,18 @@ int main(int argn, char **argv) {
         for (const KfPairCount &c : rows) std::cout << " " << c.kl_on_fov << " " << c.kl_match << " " << c.kls_on_fov << " " << c.guard;
         std::cout << "\n";
     }
+    for (int i = 0; i < N && constraint && !bad; i++)
+        for (int d = 0; d < 2; d++) {
+            KfConstraintArgs ka;
+            ka.direction = d; ka.iter_max = 10; ka.k_huber = 2.0;
+            KfConstraint kc;
+            if (!obj[i]->keyframeConstraint(ka, kc)) { std::cout << "constraint " << i << " dir " << d << ": refused\n"; continue; }
+            char buf[64];
+            std::cout << "constraint " << i << " dir " << d << ":";
+            const double v[11] = {kc.X[0], kc.X[1], kc.X[2], kc.X[3], kc.X[4], kc.X[5], kc.ratio, kc.E, kc.E0, kc.Kp, kc.W_Kp};
+            for (double x : v) { snprintf(buf, sizeof buf, " %.17g", x); std::cout << buf; }
+            std::cout << " " << kc.links << " " << kc.inliers << " " << kc.evals << " " << kc.accepted << " " << kc.guard << "\n";
+        }
     for (int i = 0; i < N; i++) obj[i]->CleanUp();
     if (bad) { std::cout << "an object stopped early: " << obj[0]->lastError() << "\n"; return 6; }
     for (int i = 0; i < N; i++) {

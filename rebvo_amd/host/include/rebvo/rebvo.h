@@ -71,6 +71,15 @@ namespace rebvo {
 // kls_on_fov's, and the KeyLines whose re-projection was not finite.
 struct KfCovisArgs { int32_t field_radius; float field_min_mod, match_mod, match_ang, rho_tol, max_r; };
 struct KfPairCount { int32_t kl_on_fov, kl_match, kls_on_fov, guard; };
+// (mirror only) REBVO::keyframeConstraint's arguments and result: edgehip_kf_constraint_args / edgehip_kf_constraint of include/edgehip.h,
+// field for field — kfvo::OptimizeRelContraint's etracket_2_keyframe, iter_max, k_huber; X, W_X, R_X, E/E0 and both terms,
+// optimizeScaleF2KF's pair, match_num of the last evaluation, the evaluations run, the steps accepted and the guard bits.
+struct KfConstraintArgs { int32_t direction, iter_max; double k_huber; };
+struct KfConstraint {
+    double X[6], W_X[36], R_X[36];
+    double ratio, E, E0, Kp, W_Kp;
+    int32_t links, inliers, evals, accepted, guard, pad;
+};
 }
 
 namespace rebvo {
@@ -535,6 +544,12 @@ public:
     // member's pairs on the way; false when the object has no group, tracks no key frames or has stopped, or when the device refuses the
     // arguments.
     bool keyframeCovisibility(const KfCovisArgs &args, std::vector<KfPairCount> &out, int &m);
+    // (mirror only) The relative-pose constraint between this object's current key frame and its newest frame: kfvo::OptimizeRelContraint
+    // (src/mtracklib/kfvo.cpp:527-604) over the links the key-frame tracking maintains, on the device (edgehip_keyframe_constraint,
+    // include/edgehip.h), for an object on the group engine with TrackKeyFrames = 1 between Init() and CleanUp().  The frame's pose is
+    // the newest nav record's Pose and Pos with the running scale K (what a key frame taken from that frame would carry).  Served by
+    // the group's thread between two steps, as keyframeCovisibility is; false under the same conditions.
+    bool keyframeConstraint(const KfConstraintArgs &args, KfConstraint &out);
     // frame-by-frame mode: no new frame is taken from the camera until advanceFrameByFrame() (rebvo.h:481-488, rebvo_first_t.cpp:154-159)
     bool toggleFrameByFrame() { return frame_by_frame = !frame_by_frame; }
     bool advanceFrameByFrame() { return frame_by_frame_advance = true; }

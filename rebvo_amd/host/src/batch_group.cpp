@@ -181,6 +181,10 @@ public:
     static_assert(sizeof(KfCovisArgs) == sizeof(edgehip_kf_covis_args) && sizeof(KfPairCount) == sizeof(edgehip_kf_pair_count), "the mirror's structs are the C ABI's");
     struct CovisReq { int seat = -1; edgehip_kf_covis_args args; std::vector<KfPairCount> *out = nullptr; int *m = nullptr; bool done = false, ok = false; };
     std::vector<CovisReq *> covis_reqs;
+    // REBVO::keyframeConstraint: the same queue discipline (covis_waiting is raised for either kind)
+    static_assert(sizeof(KfConstraintArgs) == sizeof(edgehip_kf_constraint_args) && sizeof(KfConstraint) == sizeof(edgehip_kf_constraint), "the mirror's structs are the C ABI's");
+    struct ConstraintReq { int seat = -1; edgehip_kf_constraint_args args; KfConstraint *out = nullptr; bool done = false, ok = false; };
+    std::vector<ConstraintReq *> constraint_reqs;
     std::atomic<int> covis_waiting{0};
     bool thread_done = false;
     void serveCovis();
@@ -617,10 +621,32 @@ int REBVO::BatchGroup::kfDrain(int only_seat, bool with_current) {
 void REBVO::BatchGroup::serveCovis() {
     if (!covis_waiting.load(std::memory_order_acquire)) return;
     std::vector<CovisReq *> take;
+    std::vector<ConstraintReq *> take_kc;
     {
         std::lock_guard<std::mutex> lk(mut);
         take.swap(covis_reqs);
+        take_kc.swap(constraint_reqs);
         covis_waiting.store(0, std::memory_order_release);
+    }
+    if (!take_kc.empty()) {   // the current key frames against the newest frame, with the pose a key frame taken from it would carry
+        std::vector<edgehip_nav> nav((size_t)cap);
+        std::vector<double> P((size_t)cap * 9), T((size_t)cap * 3), K((size_t)cap, 1.0);
+        std::vector<edgehip_kf_constraint> all((size_t)cap);
+        bool have = kf_track && edgehip_read_nav(hip, nav.data()) == 0;
+        for (int i = 0; i < cap && have; i++) {
+            edgehip_seq_state st;
+            have = edgehip_get_state(hip, i, &st) == 0;
+            std::memcpy(&P[(size_t)i * 9], nav[i].Pose, 72);
+            std::memcpy(&T[(size_t)i * 3], nav[i].Pos, 24);
+            K[i] = st.K;
+        }
+        for (ConstraintReq *r : take_kc) {
+            const bool ok = have && edgehip_keyframe_constraint(hip, edgehip_cur_slot(hip), P.data(), T.data(), K.data(), &r->args, all.data()) == 0;
+            if (ok) std::memcpy(r->out, &all[(size_t)r->seat], sizeof(KfConstraint));
+            std::lock_guard<std::mutex> lk(mut);
+            r->ok = ok;
+            r->done = true;
+        }
     }
     const size_t M = kKfListCapacity + 1;
     std::vector<edgehip_kf_pair_count> all((size_t)cap * M * M);
@@ -644,6 +670,8 @@ void REBVO::BatchGroup::refuseCovis() {
         thread_done = true;
         for (CovisReq *r : covis_reqs) r->done = true;
         covis_reqs.clear();
+        for (ConstraintReq *r : constraint_reqs) r->done = true;
+        constraint_reqs.clear();
     }
     cv.notify_all();
 }
@@ -657,6 +685,20 @@ bool REBVO::keyframeCovisibility(const KfCovisArgs &args, std::vector<KfPairCoun
     std::unique_lock<std::mutex> lk(g->mut);
     if (!g->started || g->thread_done || g->failed || !g->kf_track || !g->seats[group_seat].running) return false;
     g->covis_reqs.push_back(&r);
+    g->covis_waiting.store(1, std::memory_order_release);
+    g->cv.wait(lk, [&] { return r.done; });
+    return r.ok;
+}
+
+bool REBVO::keyframeConstraint(const KfConstraintArgs &args, KfConstraint &out) {
+    BatchGroup *g = group;
+    if (!g || group_seat < 0 || quit) return false;
+    BatchGroup::ConstraintReq r;
+    r.seat = group_seat; r.out = &out;
+    std::memcpy(&r.args, &args, sizeof r.args);
+    std::unique_lock<std::mutex> lk(g->mut);
+    if (!g->started || g->thread_done || g->failed || !g->kf_track || !g->seats[group_seat].running) return false;
+    g->constraint_reqs.push_back(&r);
     g->covis_waiting.store(1, std::memory_order_release);
     g->cv.wait(lk, [&] { return r.done; });
     return r.ok;
