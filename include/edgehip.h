@@ -790,7 +790,8 @@ int edgehip_ros_export_wait(edgehip_ctx *ctx, int ticket);
  * correctAugmentate (src/mtracklib/kfvo.cpp:739-771, 969-1142, 804-966); a new key frame is taken when the repaired back-match count drops
  * below min(TrackPoints, KNum) * KFSavePercent.  Here every sequence has ONE key frame in HBM, the reference's kf_list.back(); older key
  * frames go into the key-frame list below when it is enabled, and are otherwise the caller's to take when `inserted` is set.  Only
- * m_id_f of the key frame, m_id_kf of the frame lists and the counts change: nothing feeds back into the odometry.  Every id and count equals the reference's (integers; the distances behind them are fp64
+ * m_id_f of the key frame, m_id_kf of the frame lists and the counts change: nothing feeds back into the odometry, with one exception that
+ * only a caller can trigger: edgehip_keyframe_translate_depth with direction = 1 (below) writes a frame slot's rho / s_rho.  Every id and count equals the reference's (integers; the distances behind them are fp64
  * in the reference's order of operations; tests/keyframe_track_port.py restates the rule).
  * Preconditions: every p_m finite; m_id, m_id_f, m_id_kf negative or in range of the list they index.  Out-of-range links end a chain;
  * every chain walk is capped at the length of the list it walks (on finite p_m it ends before), a capped walk sets `guard`.
@@ -964,6 +965,67 @@ int edgehip_keyframe_constraint(edgehip_ctx *ctx, int slot_new, const double *Po
 int edgehip_keyframe_mutual_exclusion(edgehip_ctx *ctx, int slot_new, double dist_t, int discard_non_mutual, int kf_to_frame, int32_t *counts);
 /* Device time of the last edgehip_keyframe_constraint, by HIP events: the link gather and the solve. */
 int edgehip_keyframe_constraint_ms(edgehip_ctx *ctx, double *gather_ms, double *solve_ms);
+
+/* ---- key-frame depth along the links (kfvo::mapKFUsingIDK, translateDepth_F2KF / _KF2F / _New2Old) -----------------------------------
+ * The other half of key-frame mapping: the links the tracking above maintains MOVE depth.  Upstream defines these functions and never
+ * calls them; nothing here runs inside edgehip_process_frame.  All arithmetic is fp64 in the reference's order of operations per
+ * KeyLine (p_m, u_m: the records' floats widened); relative poses are formed as TooN forms them (row dot products from 0 in index
+ * order), on the device, the same way for every sequence (tests/keyframe_depth_port.py restates the rules).  Every rho /
+ * s_rho written equals the reference's bit for bit (NaN as a class).
+ *   result      out[nseq]: count = links used, guard, and for translate_depth K = the kf.K the rewrite used (0 for a sequence without a
+ *               key frame), rTr, rTr0 = optimizeScaleBack's sums (0 without optim_scale).
+ *   guard bit 2   a link outside the list it indexes was taken as unmatched (the reference reads out of bounds), as above
+ *   guard bit 0   optimizeScaleBack made a non-finite K: kf.K is left as it was and the rewrite runs with the old K
+ * A sequence without a key frame has no links: count 0, nothing written; no guard stops the other sequences.
+ * Pose[nseq][9], Pos[nseq][3] (and K[nseq] where the call has it) are given together, or all NULL for what edgehip_keyframe_constraint
+ * takes by default.  EDGEHIP_ERR_STATE without key-frame tracking; EDGEHIP_ERR_ARG for a slot out of range or some but not all of the
+ * pose arguments; EDGEHIP_ERR_MEMORY when the scratch (137 B x nseq, allocated by the first of these calls, freed with the key frames)
+ * cannot be allocated: the context stays usable. */
+typedef struct edgehip_kf_depth {
+    int32_t count, guard;
+    double K, rTr, rTr0;
+} edgehip_kf_depth;
+/* kfvo::mapKFUsingIDK(kf, slot_new, Pose, Pos, ReshapeQAbsolute, ReshapeQRelative, LocationUncertainty) (src/mtracklib/kfvo.cpp:1147-1184):
+ * FRelRot = Pose^T * kf.Pose, FRelPos = Pose^T * (kf.Pos - Pos), no division by a scale; one kfvo::mapKLUsingIDK (the live definition,
+ * :1276-1360, through rotateQs, include/mtracklib/kfvo.h:68-81, which returns zeros when qr[2] == 0) for every key-frame KeyLine with
+ * m_id_f >= 0 against the slot's KeyLine m_id_f, zf = cam.zfm.  The clamp chain keeps its order and its holes: rho < RHO_MIN: s_rho +=
+ * RHO_MIN - rho, rho = RHO_MIN (a NaN s_rho stays NaN); rho > RHO_MAX: rho = RHO_MAX; a NaN or infinity in either: (RhoInit, RHO_MAX);
+ * s_rho < 0: (RhoInit, RHO_MAX); RHO_MAX = 20, RHO_MIN = 1e-3, RhoInit = 1 (edge_finder.h:38-40).  Writes the key frame's rho and s_rho
+ * at linked indices and nothing else.  In-stream; synchronises only when out != NULL.  out: (links updated, guard, 0, 0, 0). */
+int edgehip_keyframe_map_depth(edgehip_ctx *ctx, int slot_new, const double *Pose, const double *Pos, double reshape_q_abs,
+                               double reshape_q_rel, double location_uncertainty, edgehip_kf_depth *out);
+/* direction 0: kfvo::translateDepth_F2KF(kf, slot_new, Pose, Pos, K, optim_scale) (:653-686): BRelRot = kf.Pose^T * Pose, BRelPos =
+ *   kf.Pose^T * (Pos - kf.Pos); with optim_scale first kf.K = optimizeScaleBack(...) (:305-341: sums over the key frame's linked
+ *   KeyLines with q1[2] > 0, through kfvo::unProject / kfvo::project, kfvo.h:42-48; summed in a fixed order of the device's own, so K,
+ *   rTr, rTr0 and what follows from K agree with the reference to rounding, and are the same bits alone and inside any batch); then
+ *   for every linked key-frame KeyLine rho = q1[2] * kf.K, s_rho = rho * (kl.s_rho / kl.rho), m_num++, with q1 =
+ *   cam.projectHomCordVec(BRelRot * cam.unprojectHomCordVec(p_m.x, p_m.y, rho) * K + BRelPos) of the slot's KeyLine m_id_f.  Writes the
+ *   key frame's rho, s_rho, m_num at linked indices, and with optim_scale the key frame's pose block K; the slot is untouched.
+ * direction 1: kfvo::translateDepth_KF2F(kf, slot_new, Pose, Pos, K) (:607-634): BRelRot = Pose^T * kf.Pose, BRelPos = Pose^T * (kf.Pos -
+ *   Pos); for every slot KeyLine with m_id_kf >= 0: rho = q1[2] * kf.K, s_rho = rho / kl.rho * kl.s_rho (the other association), q1 from
+ *   the key frame's KeyLine m_id_kf.  THIS IS THE ONE KEY-FRAME CALL THAT WRITES INTO A FRAME SLOT: the slot's rho and s_rho at linked
+ *   indices, which the next frame's tracking and mapping then read; the key frame is untouched.  (No packed per-slot copy of rho / s_rho
+ *   exists beside the arrays, so nothing else is refreshed.)  optim_scale must be 0 (EDGEHIP_ERR_ARG).
+ * In-stream; synchronises only when out != NULL. */
+int edgehip_keyframe_translate_depth(edgehip_ctx *ctx, int slot_new, int direction, const double *Pose, const double *Pos, const double *K,
+                                     int optim_scale, edgehip_kf_depth *out);
+/* kfvo::translateDepth_New2Old(kf_list, iters) (:637-650) over what the device holds of kf_list, per sequence: the held list entries,
+ * oldest first, then the current key frame (the positions of edgehip_keyframe_covisibility).  For consecutive positions (i, i + 1):
+ * translateDepth_F2KF without the scale step from i + 1 into i, with i + 1's header Pose, Pos, K and i's own K; position i's m_id_f
+ * index position i + 1's KeyLines (so it is when i + 1 was taken by the frame driver's criterion from the frame i was last repaired
+ * against, or when a caller built the list so); a link outside [0, kn of i + 1) is skipped and sets guard bit 2.  As in the
+ * reference's ascending walk every position reads its successor as it was before the iteration, and iteration n + 1 reads iteration
+ * n's results.  The list entries' rho, s_rho, m_num change in place, every other byte of the 168-byte records stays; the newest
+ * position is only read.  out[nseq] (may be NULL) = (links of the last iteration over all positions, guard, 0, 0, 0).  Synchronises.
+ * EDGEHIP_ERR_STATE without the key-frame list, EDGEHIP_ERR_ARG for iters < 0; iters == 0 does nothing. */
+int edgehip_keyframe_list_translate_depth(edgehip_ctx *ctx, int iters, edgehip_kf_depth *out);
+/* Restricts the three calls above to the sequences with mask[seq] != 0 (mask[nseq]; NULL: every sequence again, the default): the others
+ * are treated as sequences without a key frame — count 0, K 0, nothing written.  For a caller that serves one sequence's request in a
+ * batch whose other sequences did not ask (the mirror's REBVO::keyframeMapDepth).  Holds until changed or until the key frames are
+ * freed.  Synchronises (mask != NULL).  EDGEHIP_ERR_STATE without key-frame tracking. */
+int edgehip_keyframe_depth_select(edgehip_ctx *ctx, const uint8_t *mask);
+/* Device time of the last of the three calls above, by HIP events (waits for that call's end). */
+int edgehip_keyframe_depth_ms(edgehip_ctx *ctx, double *ms);
 
 /* ---- measurement ------------------------------------------------------------------------------------- */
 /* Names of the kernel groups timed by the built-in HIP-event profiler, and their accumulated device time.

@@ -86,6 +86,13 @@ struct edgehip_ctx::KfTrack {
     void *kc_arena = nullptr;
     int32_t *kc_counts = nullptr;     // [nseq][2] edgehip_keyframe_mutual_exclusion's (links seen, links kept); allocated with the key frames
     double kc_ms[2] = {0, 0};         // the last constraint call's device time: gather, solve
+    // keyframe_depth.hip's scratch, allocated by the first of its calls: the caller's poses on their way in ([nseq][13], device row and
+    // page-locked row), the results ([nseq]); events: the last call's begin and end, the last copy out of the page-locked row
+    double *kd_pose_dev = nullptr, *kd_pose_host = nullptr;
+    edgehip_kf_depth *kd_out_dev = nullptr;
+    hipEvent_t kd_ev[3] = {nullptr, nullptr, nullptr};
+    uint8_t *kd_mask_dev = nullptr;   // [nseq] edgehip_keyframe_depth_select's mask (read while kd_masked)
+    bool kd_busy = false, kd_timed = false, kd_masked = false;
 };
 
 namespace edgehip {
@@ -101,5 +108,6 @@ int kf_list_retire_one_enqueue(edgehip_ctx *c, int seq);
 int kf_entry(edgehip_ctx *c, int slot, const char *who);
 void kf_covis_free(edgehip_ctx *c);                  // keyframe_covis.hip's scratch; behind a synchronisation of c->stream; no-op when absent
 void kf_constraint_free(edgehip_ctx *c);             // keyframe_constraint.hip's scratch; the same
+void kf_depth_free(edgehip_ctx *c);                  // keyframe_depth.hip's scratch; the same
 
 }  // namespace edgehip

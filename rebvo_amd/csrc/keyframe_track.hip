@@ -448,6 +448,7 @@ void edgehip::kf_track_free(edgehip_ctx *c) {
     kf_list_free(c);
     kf_covis_free(c);
     kf_constraint_free(c);
+    kf_depth_free(c);
     for (void *q : d->dev) (void)hipFree(q);
     if (d->pose12_host) (void)hipHostFree(d->pose12_host);
     if (d->blk_host) (void)hipHostFree(d->blk_host);

@@ -273,6 +273,15 @@ class KfConstraint(C.Structure):
 
 KF_CONSTRAINT_DTYPE = np.dtype(KfConstraint)
 assert KF_CONSTRAINT_DTYPE.itemsize == 688 and C.sizeof(KfConstraintArgs) == 16
+
+
+class KfDepth(C.Structure):
+    """edgehip_kf_depth: links used, guard bits, the kf.K the rewrite used and optimizeScaleBack's two sums."""
+    _fields_ = [("count", C.c_int32), ("guard", C.c_int32), ("K", C.c_double), ("rTr", C.c_double), ("rTr0", C.c_double)]
+
+
+KF_DEPTH_DTYPE = np.dtype(KfDepth)
+assert KF_DEPTH_DTYPE.itemsize == 32
 NAV_DTYPE = np.dtype(Nav)   # numpy view of edgehip_nav (same offsets as the ctypes struct)
 assert NAV_DTYPE.itemsize == C.sizeof(Nav)
 
@@ -310,6 +319,8 @@ EXPORTS = [
     "edgehip_download_keyframe_list_batch", "edgehip_keyframe_list_restore",
     "edgehip_keyframe_covisibility", "edgehip_keyframe_covisibility_slot", "edgehip_keyframe_covisibility_ms",
     "edgehip_keyframe_constraint", "edgehip_keyframe_mutual_exclusion", "edgehip_keyframe_constraint_ms",
+    "edgehip_keyframe_map_depth", "edgehip_keyframe_translate_depth", "edgehip_keyframe_list_translate_depth", "edgehip_keyframe_depth_ms",
+    "edgehip_keyframe_depth_select",
 ]
 
 _lib = None
@@ -1317,6 +1328,61 @@ class EdgeHip:
         g, s = C.c_double(0), C.c_double(0)
         self._ck(self.lib.edgehip_keyframe_constraint_ms(self.ctx, C.byref(g), C.byref(s)))
         return g.value, s.value
+
+    # ---- key-frame depth along the links (kfvo::mapKFUsingIDK, translateDepth_F2KF / _KF2F / _New2Old) ----
+    def _kf_depth_pose(self, Pose, Pos, K, with_K):
+        given = [x is not None for x in ((Pose, Pos, K) if with_K else (Pose, Pos))]
+        if not any(given):
+            return None, None, None, None
+        assert all(given), "Pose, Pos and K are given together" if with_K else "Pose and Pos are given together"
+        P = np.ascontiguousarray(np.broadcast_to(np.asarray(Pose, np.float64).reshape(-1, 9), (self.nseq, 9)))
+        T = np.ascontiguousarray(np.broadcast_to(np.asarray(Pos, np.float64).reshape(-1, 3), (self.nseq, 3)))
+        S = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1), (self.nseq,))) if with_K else None
+        return _dp(P), _dp(T), (None if S is None else _dp(S)), (P, T, S)
+
+    @staticmethod
+    def _kf_depth_result(out):
+        return None if out is None else {k: out[k].copy() for k in out.dtype.names}
+
+    def keyframe_map_depth(self, slot_new, reshape_q_abs, reshape_q_rel, location_uncertainty, Pose=None, Pos=None, want_result=True):
+        """mapKFUsingIDK of every sequence's current key frame against ring slot `slot_new` -> a dict of arrays (nseq,): count, guard, K,
+        rTr, rTr0 (the last three 0), or None (and no synchronisation) when want_result is False.  Pose (nseq, 3, 3) and Pos (nseq, 3)
+        are given together, or both None for Pose*R and Pos - Pose*R*V*K from seq_state."""
+        out = np.zeros(self.nseq, KF_DEPTH_DTYPE) if want_result else None
+        pp, pt, _, keep = self._kf_depth_pose(Pose, Pos, None, False)
+        self._ck(self.lib.edgehip_keyframe_map_depth(self.ctx, int(slot_new), pp, pt, C.c_double(reshape_q_abs), C.c_double(reshape_q_rel),
+                                                     C.c_double(location_uncertainty), None if out is None else out.ctypes.data_as(C.c_void_p)))
+        return self._kf_depth_result(out)
+
+    def keyframe_translate_depth(self, slot_new, direction, optim_scale=False, Pose=None, Pos=None, K=None, want_result=True):
+        """direction 0: translateDepth_F2KF (the slot's depth into the key frame, optim_scale first re-estimates the key frame's K);
+        direction 1: translateDepth_KF2F (the key frame's depth into the SLOT's rho / s_rho) -> a dict of arrays (nseq,): count, guard,
+        K (the kf.K used), rTr, rTr0, or None (and no synchronisation) when want_result is False.  Pose, Pos and K (nseq,) are given
+        together, or all None for the defaults of keyframe_constraint."""
+        out = np.zeros(self.nseq, KF_DEPTH_DTYPE) if want_result else None
+        pp, pt, pk, keep = self._kf_depth_pose(Pose, Pos, K, True)
+        self._ck(self.lib.edgehip_keyframe_translate_depth(self.ctx, int(slot_new), int(direction), pp, pt, pk, int(bool(optim_scale)),
+                                                           None if out is None else out.ctypes.data_as(C.c_void_p)))
+        return self._kf_depth_result(out)
+
+    def keyframe_list_translate_depth(self, iters):
+        """translateDepth_New2Old over every sequence's held list entries (oldest first) and its current key frame -> a dict of arrays
+        (nseq,): count (links of the last iteration), guard, K, rTr, rTr0 (0)."""
+        out = np.zeros(self.nseq, KF_DEPTH_DTYPE)
+        self._ck(self.lib.edgehip_keyframe_list_translate_depth(self.ctx, int(iters), out.ctypes.data_as(C.c_void_p)))
+        return self._kf_depth_result(out)
+
+    def keyframe_depth_select(self, mask=None):
+        """Restrict the three calls above to the sequences with mask[seq] true (None: every sequence again)."""
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(bool), np.uint8)
+        assert m is None or m.shape == (self.nseq,)
+        self._ck(self.lib.edgehip_keyframe_depth_select(self.ctx, None if m is None else m.ctypes.data_as(C.c_void_p)))
+
+    def keyframe_depth_ms(self):
+        """-> device ms of the last of the three calls above, by HIP events."""
+        ms = C.c_double(0)
+        self._ck(self.lib.edgehip_keyframe_depth_ms(self.ctx, C.byref(ms)))
+        return ms.value
 
     def download_plane(self, seq, which):
         idx = {"img0": 0, "img1": 1, "dog": 2, "dx": 3, "dy": 4}[which]

@@ -3,7 +3,7 @@
 // REBVO::kf_list goes into a key-frame file the reference's kf_visualizer loads.  Used by tests/test_keyframe_host_gpu.py.
 //
 //   keyframe_replay <GlobalConfig> <frames.rgb24> <objects> <frames_per_object> <t0> <dt> <out_prefix>
-//                   [--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis] [--constraint]
+//                   [--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis] [--constraint] [--depth]
 //
 // frames.rgb24 = objects x frames_per_object x ImageHeight x ImageWidth x 3 bytes: object i's frame k is frame i * frames_per_object + k
 // and carries the stamp t0 + k dt.  --group puts all objects into one batch group of that name (without it every object has its own
@@ -18,6 +18,12 @@
 // --constraint: at the same point, REBVO::keyframeConstraint of every object in both directions with (iter_max, k_huber) = (10, 2): the
 // current key frame against the newest frame.  Prints "constraint <i> dir <d>:" and X[6], ratio, E, E0, Kp, W_Kp with 17 significant
 // digits, then links, inliers, evals, accepted, guard.
+// --depth: REBVO::keyframeMapDepth of every object with (ReshapeQAbsolute, ReshapeQRelative, LocationUncertainty) = (1e-3, 5e-2, 2) after
+// every frame but the first (the objects are then stepped frame by frame: each frame's record is waited for).  Prints "mapdepth <i> frame <k>: <count>";
+// before CleanUp(), REBVO::keyframeTranslateDepth (0, optim_scale) and then (1, false) of every object: "translate <i> dir <d>:" and
+// count, guard, K, rTr, rTr0 (17 significant digits).  With or without the flag the run ends with "depth <i>: median s_rho <x> of <n>
+// KeyLines" for every object's current key frame (the last entry of its kf_list), so two runs show what the flag did to it.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -81,7 +87,7 @@ static int map_views(const REBVOParameters &prm, std::vector<keyframe> &list) {
 int main(int argn, char **argv) {
     if (argn < 8) {
         std::cout << "usage: keyframe_replay <GlobalConfig> <frames.rgb24> <objects> <frames_per_object> <t0> <dt> <out_prefix> "
-                     "[--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis] [--constraint]\n";
+                     "[--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis] [--constraint] [--depth]\n";
         return 2;
     }
     const int N = atoi(argv[3]), K = atoi(argv[4]);
@@ -89,7 +95,7 @@ int main(int argn, char **argv) {
     const std::string prefix = argv[7];
     std::string group;
     int start = -1, end = -1;
-    bool disagree = false, map = false, covis = false, constraint = false;
+    bool disagree = false, map = false, covis = false, constraint = false, depth = false;
     for (int a = 8; a < argn; a++) {
         const std::string s = argv[a];
         if (s == "--group" && a + 1 < argn) group = argv[++a];
@@ -99,6 +105,7 @@ int main(int argn, char **argv) {
         else if (s == "--map") map = true;
         else if (s == "--covis") covis = true;
         else if (s == "--constraint") constraint = true;
+        else if (s == "--depth") depth = true;
         else { std::cout << "unknown argument " << s << "\n"; return 2; }
     }
     if (N < 1 || K < 2) { std::cout << "bad counts\n"; return 2; }
@@ -127,7 +134,16 @@ int main(int argn, char **argv) {
             return 4;
         }
     bool bad = false;
-    for (int k = 0; k < K && !bad; k++)
+    const auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(60);
+    // every object's record of the frame stamped t
+    auto wait_for = [&](double t) {
+        for (int i = 0; i < N && !bad; i++)
+            while (obj[i]->getNav().t < t - 1e-9 * (1 + std::fabs(t))) {
+                if (!obj[i]->Running() || std::chrono::steady_clock::now() > deadline) { bad = true; break; }
+                std::this_thread::sleep_for(std::chrono::microseconds(100));
+            }
+    };
+    for (int k = 0; k < K && !bad; k++) {
         for (int i = 0; i < N && !bad; i++) {
             if (k == start) obj[i]->startKeyFrames();
             if (k == end) obj[i]->endKeyFrames();
@@ -138,14 +154,16 @@ int main(int argn, char **argv) {
             (*ptr).copyFrom(reinterpret_cast<const RGB24Pixel *>(pool.data() + fb * ((size_t)i * K + k)));
             obj[i]->releaseCustomCamBuffer();
         }
-    // every object's record of its last frame, then the end
-    const double t_last = t0 + dt * (K - 1);
-    const auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(60);
-    for (int i = 0; i < N && !bad; i++)
-        while (obj[i]->getNav().t < t_last - 1e-9 * (1 + std::fabs(t_last))) {
-            if (!obj[i]->Running() || std::chrono::steady_clock::now() > deadline) { bad = true; break; }
-            std::this_thread::sleep_for(std::chrono::microseconds(100));
+        if (!depth || k == 0) continue;   // (the first frame has no record and no key frame)
+        wait_for(t0 + dt * k);
+        for (int i = 0; i < N && !bad; i++) {
+            int count = 0;
+            if (!obj[i]->keyframeMapDepth(1e-3, 5e-2, 2.0, count)) { std::cout << "mapdepth " << i << " frame " << k << ": refused\n"; continue; }
+            std::cout << "mapdepth " << i << " frame " << k << ": " << count << "\n";
         }
+    }
+    // every object's record of its last frame, then the end
+    wait_for(t0 + dt * (K - 1));
     for (int i = 0; i < N && covis && !bad; i++) {
         KfCovisArgs ca;
         ca.field_radius = (int)prm.SearchRange; ca.field_min_mod = 0.f;
@@ -170,12 +188,29 @@ int main(int argn, char **argv) {
             for (double x : v) { snprintf(buf, sizeof buf, " %.17g", x); std::cout << buf; }
             std::cout << " " << kc.links << " " << kc.inliers << " " << kc.evals << " " << kc.accepted << " " << kc.guard << "\n";
         }
+    for (int i = 0; i < N && depth && !bad; i++)
+        for (int d = 0; d < 2; d++) {
+            KfDepth kd;
+            if (!obj[i]->keyframeTranslateDepth(d, d == 0, kd)) { std::cout << "translate " << i << " dir " << d << ": refused\n"; continue; }
+            char buf[64];
+            std::cout << "translate " << i << " dir " << d << ": " << kd.count << " " << kd.guard;
+            for (double x : {kd.K, kd.rTr, kd.rTr0}) { snprintf(buf, sizeof buf, " %.17g", x); std::cout << buf; }
+            std::cout << "\n";
+        }
     for (int i = 0; i < N; i++) obj[i]->CleanUp();
     if (bad) { std::cout << "an object stopped early: " << obj[0]->lastError() << "\n"; return 6; }
     for (int i = 0; i < N; i++) {
         const std::string name = prefix + "kf_" + std::to_string(i) + ".kf";
         if (!keyframe::saveKeyframes2File(name.c_str(), obj[i]->kf_list)) { std::cout << "cannot write " << name << "\n"; return 7; }
         std::cout << "object " << i << ": " << obj[i]->kf_list.size() << " key frames\n";
+        if (!obj[i]->kf_list.empty()) {   // the current key frame's depth uncertainty
+            std::vector<double> s;
+            for (const KeyLine &kl : obj[i]->kf_list.back().kl) s.push_back(kl.s_rho);
+            std::sort(s.begin(), s.end());
+            char buf[64];
+            snprintf(buf, sizeof buf, "%.17g", s.empty() ? 0.0 : s[s.size() / 2]);
+            std::cout << "depth " << i << ": median s_rho " << buf << " of " << s.size() << " KeyLines\n";
+        }
     }
     if (map && map_views(prm, obj[0]->kf_list) != 0) return 8;
     return 0;

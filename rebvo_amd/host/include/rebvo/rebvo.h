@@ -80,6 +80,9 @@ struct KfConstraint {
     double ratio, E, E0, Kp, W_Kp;
     int32_t links, inliers, evals, accepted, guard, pad;
 };
+// (mirror only) REBVO::keyframeTranslateDepth's result: edgehip_kf_depth of include/edgehip.h, field for field — the links used, the guard
+// bits, the key frame's K the rewrite used and optimizeScaleBack's two sums.
+struct KfDepth { int32_t count, guard; double K, rTr, rTr0; };
 }
 
 namespace rebvo {
@@ -461,6 +464,7 @@ class REBVO {
     std::map<const PipeBuffer *, std::unique_ptr<EdgeMapMsg>> em_msgs;
     BatchGroup *group = nullptr;
     int group_seat = -1;
+    bool keyframeDepthRequest(void *req);   // keyframeMapDepth / keyframeTranslateDepth: a BatchGroup::DepthReq through the group's queue
     customCam::CustomCamPipeBuffer *cam_cur = nullptr;   // the buffer the application holds between request and releaseCustomCamBuffer
     customCam::CustomCamPipeBuffer *cam_cur_pair = nullptr;   // ... and between requestStereoCustomCamBuffer and releaseStereoCustomCamBuffer
     void groupFrameWritten(customCam::CustomCamPipeBuffer *b, bool pair = false);
@@ -550,6 +554,17 @@ public:
     // the newest nav record's Pose and Pos with the running scale K (what a key frame taken from that frame would carry).  Served by
     // the group's thread between two steps, as keyframeCovisibility is; false under the same conditions.
     bool keyframeConstraint(const KfConstraintArgs &args, KfConstraint &out);
+    // (mirror only) Depth along the links between this object's current key frame and its newest frame, on the device
+    // (edgehip_keyframe_map_depth / edgehip_keyframe_translate_depth, include/edgehip.h), for an object on the group engine with
+    // TrackKeyFrames = 1 between Init() and CleanUp(); the frame is the newest slot, its pose the newest nav record's with the running K,
+    // as for keyframeConstraint.  keyframeMapDepth: kfvo::mapKFUsingIDK (src/mtracklib/kfvo.cpp:1147-1184), one EKF update of every linked
+    // key-frame KeyLine's inverse depth; count = the links updated.  keyframeTranslateDepth: direction 0 kfvo::translateDepth_F2KF
+    // (:653-686; optim_scale re-estimates the key frame's K first), direction 1 kfvo::translateDepth_KF2F (:607-634), which writes the
+    // FRAME's rho / s_rho — the one call here that feeds back into this object's odometry.  Only this object's key frame and frame are
+    // touched (edgehip_keyframe_depth_select), whatever the other members of the group do.  Served by the group's thread between two
+    // steps, as keyframeConstraint is; false under the same conditions.
+    bool keyframeMapDepth(double q_abs, double q_rel, double loc_unc, int &count);
+    bool keyframeTranslateDepth(int direction, bool optim_scale, KfDepth &result);
     // frame-by-frame mode: no new frame is taken from the camera until advanceFrameByFrame() (rebvo.h:481-488, rebvo_first_t.cpp:154-159)
     bool toggleFrameByFrame() { return frame_by_frame = !frame_by_frame; }
     bool advanceFrameByFrame() { return frame_by_frame_advance = true; }

@@ -185,6 +185,10 @@ public:
     static_assert(sizeof(KfConstraintArgs) == sizeof(edgehip_kf_constraint_args) && sizeof(KfConstraint) == sizeof(edgehip_kf_constraint), "the mirror's structs are the C ABI's");
     struct ConstraintReq { int seat = -1; edgehip_kf_constraint_args args; KfConstraint *out = nullptr; bool done = false, ok = false; };
     std::vector<ConstraintReq *> constraint_reqs;
+    // REBVO::keyframeMapDepth / keyframeTranslateDepth: the same queue; map: the three reshape arguments, otherwise direction and optim_scale
+    static_assert(sizeof(KfDepth) == sizeof(edgehip_kf_depth), "the mirror's struct is the C ABI's");
+    struct DepthReq { int seat = -1; bool map = false; double q[3] = {0, 0, 0}; int direction = 0, optim_scale = 0; KfDepth *out = nullptr; bool done = false, ok = false; };
+    std::vector<DepthReq *> depth_reqs;
     std::atomic<int> covis_waiting{0};
     bool thread_done = false;
     void serveCovis();
@@ -622,16 +626,20 @@ void REBVO::BatchGroup::serveCovis() {
     if (!covis_waiting.load(std::memory_order_acquire)) return;
     std::vector<CovisReq *> take;
     std::vector<ConstraintReq *> take_kc;
+    std::vector<DepthReq *> take_kd;
     {
         std::lock_guard<std::mutex> lk(mut);
         take.swap(covis_reqs);
         take_kc.swap(constraint_reqs);
+        take_kd.swap(depth_reqs);
         covis_waiting.store(0, std::memory_order_release);
     }
-    if (!take_kc.empty()) {   // the current key frames against the newest frame, with the pose a key frame taken from it would carry
+    if (!take_kc.empty() || !take_kd.empty()) {   // the current key frames against the newest frame, with the pose a key frame taken from it would carry
         std::vector<edgehip_nav> nav((size_t)cap);
         std::vector<double> P((size_t)cap * 9), T((size_t)cap * 3), K((size_t)cap, 1.0);
         std::vector<edgehip_kf_constraint> all((size_t)cap);
+        std::vector<edgehip_kf_depth> all_kd((size_t)cap);
+        std::vector<uint8_t> mask((size_t)cap);
         bool have = kf_track && edgehip_read_nav(hip, nav.data()) == 0;
         for (int i = 0; i < cap && have; i++) {
             edgehip_seq_state st;
@@ -643,6 +651,21 @@ void REBVO::BatchGroup::serveCovis() {
         for (ConstraintReq *r : take_kc) {
             const bool ok = have && edgehip_keyframe_constraint(hip, edgehip_cur_slot(hip), P.data(), T.data(), K.data(), &r->args, all.data()) == 0;
             if (ok) std::memcpy(r->out, &all[(size_t)r->seat], sizeof(KfConstraint));
+            std::lock_guard<std::mutex> lk(mut);
+            r->ok = ok;
+            r->done = true;
+        }
+        for (DepthReq *r : take_kd) {   // these WRITE: the request's seat alone
+            std::fill(mask.begin(), mask.end(), (uint8_t)0);
+            mask[(size_t)r->seat] = 1;
+            bool ok = have && edgehip_keyframe_depth_select(hip, mask.data()) == 0;
+            if (ok) {
+                const int slot = edgehip_cur_slot(hip);
+                ok = (r->map ? edgehip_keyframe_map_depth(hip, slot, P.data(), T.data(), r->q[0], r->q[1], r->q[2], all_kd.data())
+                             : edgehip_keyframe_translate_depth(hip, slot, r->direction, P.data(), T.data(), K.data(), r->optim_scale, all_kd.data())) == 0;
+                ok = edgehip_keyframe_depth_select(hip, nullptr) == 0 && ok;
+            }
+            if (ok) std::memcpy(r->out, &all_kd[(size_t)r->seat], sizeof(KfDepth));
             std::lock_guard<std::mutex> lk(mut);
             r->ok = ok;
             r->done = true;
@@ -672,6 +695,8 @@ void REBVO::BatchGroup::refuseCovis() {
         covis_reqs.clear();
         for (ConstraintReq *r : constraint_reqs) r->done = true;
         constraint_reqs.clear();
+        for (DepthReq *r : depth_reqs) r->done = true;
+        depth_reqs.clear();
     }
     cv.notify_all();
 }
@@ -702,6 +727,34 @@ bool REBVO::keyframeConstraint(const KfConstraintArgs &args, KfConstraint &out) 
     g->covis_waiting.store(1, std::memory_order_release);
     g->cv.wait(lk, [&] { return r.done; });
     return r.ok;
+}
+
+bool REBVO::keyframeDepthRequest(void *req) {
+    BatchGroup *g = group;
+    if (!g || group_seat < 0 || quit) return false;
+    BatchGroup::DepthReq &r = *static_cast<BatchGroup::DepthReq *>(req);
+    r.seat = group_seat;
+    std::unique_lock<std::mutex> lk(g->mut);
+    if (!g->started || g->thread_done || g->failed || !g->kf_track || !g->seats[group_seat].running) return false;
+    g->depth_reqs.push_back(&r);
+    g->covis_waiting.store(1, std::memory_order_release);
+    g->cv.wait(lk, [&] { return r.done; });
+    return r.ok;
+}
+
+bool REBVO::keyframeMapDepth(double q_abs, double q_rel, double loc_unc, int &count) {
+    BatchGroup::DepthReq r;
+    KfDepth out;
+    r.map = true; r.q[0] = q_abs; r.q[1] = q_rel; r.q[2] = loc_unc; r.out = &out;
+    if (!keyframeDepthRequest(&r)) return false;
+    count = out.count;
+    return true;
+}
+
+bool REBVO::keyframeTranslateDepth(int direction, bool optim_scale, KfDepth &result) {
+    BatchGroup::DepthReq r;
+    r.direction = direction; r.optim_scale = optim_scale; r.out = &result;
+    return keyframeDepthRequest(&r);
 }
 
 // One frame of every running member, or false.  block: wait (in 1 ms slices, watching the quit flags) until they are all there;

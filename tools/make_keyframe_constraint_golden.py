@@ -335,7 +335,9 @@ def crafted(exe):
     return rec
 
 
-def chained(exe, ref_root, tmp, w=256, h=192, n_frames=4, keep=(2, 3)):
+def chained_pairs(ref_root, tmp, w=256, h=192, n_frames=4, keep=(2, 3)):
+    """-> (pairs of frame 0 as key frame against the frames `keep`, cam, the frames); tools/make_keyframe_depth_golden.py builds its
+    chained fixture from the same pairs."""
     import keyframe_track_port as tport
     import make_keyframe_track_golden as tg
     from oracle import oracle
@@ -371,6 +373,11 @@ def chained(exe, ref_root, tmp, w=256, h=192, n_frames=4, keep=(2, 3)):
             pairs.append(dict(kf=dict(lst(kf0["kl"]), m_id_f=m_id_f.copy()), fr=dict(lst(fr["kl"]), m_id_kf=m_id_kf_prev.copy()),
                               kf_Pose=kf0["Pose"], kf_Pos=kf0["Pos"], kf_K=np.float64(kf0["K"]), Pose=fr["Pose"], Pos=fr["Pos"], K=np.float64(fr["K"]),
                               zfm=float(cam["zfm"]), kind="compared"))
+    return pairs, cam, frames
+
+
+def chained(exe, ref_root, tmp):
+    pairs, cam, _ = chained_pairs(ref_root, tmp)
     cases = case_list(range(len(pairs)), iters=(10,))
     refs, stats, seconds = run_cases(exe, np.random.RandomState(1), pairs, cam, cases, "chained", drop=True)
     if len(cases) < 8 or len({(c["direction"], c["k_huber"] > 0) for c in cases}) < 4:
