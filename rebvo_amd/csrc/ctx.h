@@ -32,13 +32,12 @@ constexpr int kBandRows = 12;       // rows per detect block (+4 halo rows in LD
 constexpr int kDetWaves = 16;       // waves per detect block; a (band, wave) strip is the raster-order compaction granule
 constexpr int kDivLutMax = 256;     // reciprocal-count LUT entries (box width up to 15)
 constexpr int kTvrThreads = 256;    // threads per TryVelRot block (more KeyLines per block — bigger blocks or several passes — measured slower: the kernel lives on occupancy to hide its two dependent gathers)
-constexpr int kTvrPasses = 1;       // KeyLines per thread
-constexpr int kTvrBlock = kTvrThreads * kTvrPasses;   // KeyLines per block = granule of the residual carries
+constexpr int kTvrBlock = kTvrThreads;   // KeyLines per block (one per thread) = granule of the residual carries
 constexpr int kNumSums = 28;        // 21 JtJ + 6 JtF + score
 constexpr int kRefRing = 8;         // CBUFSIZE of the reference (frame ring length that FrameCount semantics follow)
 constexpr int kResidBufs = 3;       // Res0, Res1, Rest (global_tracker.cpp:611)
 
-// "inherit the last valid residual of the previous blocks" marker in residual buffers (see stage_b.hip)
+// "inherit the last valid residual of the previous blocks" marker in residual buffers (see resid_carry.h)
 __host__ __device__ inline uint64_t resid_carry_bits() { return 0x7FF8C0DEC0DEC0DEull; }
 
 // One record per KeyLine gathered at random by TryVelRot / search_match: 32 B, one 2x16-B load.

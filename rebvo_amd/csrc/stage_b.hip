@@ -18,10 +18,9 @@
 //
 // Sequential quirks of the reference restated as parallel rules:
 //  * DResidualNew[ikl] = fi where `fi` is only refreshed by a successful match (global_tracker.cpp:344,
-//    391, 406): an unmatched KeyLine inherits the residual of the last matched KeyLine before it.  Inside
-//    a block this is a "last valid" scan (ballot + shuffle, then LDS across waves); across blocks the
-//    value is written as a marker NaN and resolved by the next reader from per-block carries that
-//    k_lm_step prefixes.
+//    391, 406): an unmatched KeyLine inherits the residual of the last matched KeyLine before it.  The
+//    whole protocol — wave, block, marker NaN, per-block carries — is stated and implemented once, in
+//    resid_carry.h.
 //  * build_field keeps, per pixel, the smallest |t| and among equals the LAST KeyLine: one atomicMin on
 //    (dist << 16 | 0xFFFF - ikl) in an LDS tile; what reaches HBM is the winner's index alone (2 bytes: the evaluation
 //    never reads the distance), 8x4-pixel tiles so that the KeyLines of an edge share cache lines.
@@ -37,6 +36,7 @@
 #include <type_traits>
 
 #include "ctx.h"
+#include "resid_carry.h"
 #include "wave_reduce.h"
 
 namespace edgehip {
@@ -771,8 +771,6 @@ __device__ __forceinline__ double rsqrt_f64(double x) {
     return x > 1e300 ? 0.0 : y;   // 1 / sqrt(inf) = 0 as the reference's x / sqrt(inf) gives; NaN stays NaN
 }
 
-__device__ __forceinline__ bool is_carry(double v) { return __double_as_longlong(v) == (long long)resid_carry_bits(); }
-
 // KF = kfvo::TryVelRot (src/mtracklib/kfvo.cpp:1389-1668), the key-frame flavour of the same evaluation: the KeyLines of the
 // current frame (kl_old here) against the field of a key frame (kl_new).  It differs from global_tracker::TryVelRot in four
 // places: the match-count gate ignores FrameCount (:1441), the gradient is not z-rotated (:1476-1478 are commented out),
@@ -799,6 +797,42 @@ __device__ __forceinline__ bool is_carry(double v) { return __double_as_longlong
 #ifndef EDGEHIP_TVR_ABL
 #define EDGEHIP_TVR_ABL 0   // timing experiments only (tools/experiments/exp_tvr_ablate.sh): 1 no cross-lane reduction, 2 no div/sqrt,
 #endif                      // 4 no matched-KeyLine gather, 8 no field gather, 16 no residual stream
+// The matched KeyLine's c_p, m_m, u_m.  GREC: a 16-byte record (four records share the 64 bytes a random gather moves, instead of
+// two) that leaves u_m to grec_u_m below, valid for KeyLines nothing has rotated since detection; else the 32-byte MatchRec.
+template <bool GREC>
+__device__ __forceinline__ void load_matched(const KlSoA &kl, const int ikf, float &cpx, float &cpy, float &mx, float &my, float &ux, float &uy) {
+    if (GREC) {
+        const float4 g = ldg(kl.grec, ikf);
+        cpx = g.x; cpy = g.y; mx = g.z; my = g.w;
+    } else {
+        const MatchRec fr = kl.rec[ikf];
+        cpx = fr.c_px; cpy = fr.c_py; mx = fr.m_mx; my = fr.m_my; ux = fr.u_mx; uy = fr.u_my;
+    }
+}
+// u_m = m_m / |m_m| recomputed with the detector's own float expressions (k_emit; edge_finder.cpp:166-200)
+__device__ __forceinline__ void grec_u_m(const float mx, const float my, float &ux, float &uy) {
+    const float n2m = mx * mx + my * my;
+    const float nm = sqrtf_mid(n2m);
+    div2_mid_f32(mx, my, nm, ux, uy);
+}
+
+// The Jacobian row of a KeyLine (global_tracker.cpp:419-450: MulVect / MlAcVect chains, one rounding per statement), T = double or float
+template <typename T>
+__device__ __forceinline__ void jac_row(T (&J)[6], const T zf, const T rho_p, const T pix, const T piy, const T ptx, const T pty, const T ptz,
+                                        const T dfx, const T dfy) {
+    T t0 = zf * rho_p;
+    J[0] = t0 * dfx;
+    J[1] = t0 * dfy;
+    t0 = rho_p * pix;
+    J[2] = t0 * dfx;
+    t0 = rho_p * piy;
+    J[2] += t0 * dfy;
+    J[3] = J[1] * ptz; J[3] += J[2] * pty;
+    J[4] = J[0] * ptz; J[4] += J[2] * ptx;
+    t0 = J[0] * pty;
+    J[5] = (T)-1 * t0; J[5] += J[1] * ptx;
+}
+
 template <bool REWEIGHT, bool PROCJF, bool GREC, bool KF = false>
 __device__ __forceinline__ void tvr_body(const TvrArgs &a, const int seq, const int blk, const int tid) {
     constexpr int ABL = KF ? 0 : EDGEHIP_TVR_ABL;
@@ -811,283 +845,226 @@ __device__ __forceinline__ void tvr_body(const TvrArgs &a, const int seq, const 
     const double *rin = a.resid + ((size_t)res_in * a.nseq + seq) * a.cap;
     double *rout = a.resid + ((size_t)res_out * a.nseq + seq) * a.cap;
     const double carry_in_prev = a.resid_carry[((size_t)res_in * a.nseq + seq) * a.nblk + blk];
-    const double marker = __longlong_as_double((long long)resid_carry_bits());
 
-    // A block owns kTvrBlock consecutive KeyLines and walks them in kTvrPasses passes of kTvrThreads (pass p, thread
-    // t -> KeyLine blk*kTvrBlock + p*kTvrThreads + t: coalesced, and KeyLine order = (pass, thread) order).  The 28
-    // products of every pass accumulate in registers; the cross-lane reduction runs once per block instead of once
-    // per KeyLine.
+    // A block owns kTvrBlock consecutive KeyLines, one per thread (thread t -> KeyLine blk*kTvrBlock + t: coalesced, and KeyLine
+    // order = thread order).
     constexpr int NW = kTvrThreads / 64;   // waves per block
-    constexpr bool GRAM_MFMA = PROCJF && kTvrPasses == 1 && EDGEHIP_TVR_MFMA && !(ABL & 1);
+    constexpr bool GRAM_MFMA = PROCJF && EDGEHIP_TVR_MFMA && !(ABL & 1);
     __shared__ double s_rows[GRAM_MFMA ? NW : 1][GRAM_MFMA ? 64 : 1][8];
-    __shared__ double s_wlast[kTvrPasses][NW];
-    __shared__ int s_whas[kTvrPasses][NW];
+    __shared__ double s_wlast[NW];
+    __shared__ int s_whas[NW];
     double sums[kNumSums];
 #pragma unroll
     for (int i = 0; i < kNumSums; i++) sums[i] = 0;
 
-#pragma unroll 1
-    for (int pass = 0; pass < kTvrPasses; pass++) {
-        const int base = blk * kTvrBlock + pass * kTvrThreads;
-        if (base >= kn) break;               // block-uniform
-        const int ikl = base + tid;
-        double J[6] = {0, 0, 0, 0, 0, 0};
-        double fm, dfx, dfy;   // (set where the evaluation begins: `if (!skip)`)
-        // What only an evaluated KeyLine (status != 0) reads further down is left without a default: a default is a register move at every
-        // level of the nest below (the compiler materialised 44 v_mov_b64 for them, 8 % of the evaluation's vector instructions), and the
-        // Jacobian section now runs for evaluated KeyLines only (a skipped one contributed exact zeros: J = 0, fm = 0 stand for it).
-        double ptx, pty, ptz, pix, piy, rho_p, s_rho;
+    const int ikl = blk * kTvrBlock + tid;
+    double J[6] = {0, 0, 0, 0, 0, 0};
+    double fm, dfx, dfy;   // (set where the evaluation begins: `if (!skip)`)
+    // What only an evaluated KeyLine (status != 0) reads further down is left without a default: a default is a register move at every
+    // level of the nest below (the compiler materialised 44 v_mov_b64 for them, 8 % of the evaluation's vector instructions), and the
+    // Jacobian section now runs for evaluated KeyLines only (a skipped one contributed exact zeros: J = 0, fm = 0 stand for it).
+    double ptx, pty, ptz, pix, piy, rho_p, s_rho;
 #if EDGEHIP_TVR_REF_ORDER
-        double wgt_ref;      // the Huber weight (REWEIGHT)
+    double wgt_ref;      // the Huber weight (REWEIGHT)
 #else
-        double inv_w2 = 1;   // 1 / weight^2 (REWEIGHT)
+    double inv_w2 = 1;   // 1 / weight^2 (REWEIGHT)
 #endif
-        int mid_f = -1;
-        // status: 0 = skipped (no residual written), 1 = out of image (max_r), 2 = evaluated & matched (own fi),
-        //         3 = evaluated, unmatched (inherits the previous valid fi)
-        int status = 0;
-        double fi = 0;        // (every lane hands it to the shuffles below: it keeps its default)
-        double rho_own;       // the KeyLine's rho, kept for the key post of the last evaluation (no load behind the residual store); read with mid_f >= 0 only
-        if (ikl < kn) {
-            // Everything the KeyLine streams in is requested here, before the first use: the skip test, the projection, the
-            // in-image test and the two gathers are a chain of dependent memory round trips, and with the loads inside the
-            // branches each level of the chain paid its own.  (The ~10 % of KeyLines the tests drop load 36 B in vain.)
-            s_rho = ldg(ko.s_rho, ikl);
-            const int32_t mnum = ldg(ko.m_num, ikl);
-            const float2 pm0 = ldg(ko.p_m, ikl);
-            const double rho0 = ldg(ko.rho, ikl);
-            rho_own = rho0;
-            const float2 klm = ldg(ko.m_m, ikl);
-            const float knm = ldg(ko.n_m, ikl);
-            double rprev = 0;
-            if (REWEIGHT && !(ABL & 16)) rprev = rin[ikl];
-            const uint32_t fc = KF ? 0xFFFFFFFFu : a.framecount[seq];
-            const uint32_t mthr = a.match_num_thresh < fc ? a.match_num_thresh : fc;
-            const bool skip = s_rho > sq->s_rho_min_eval || (uint32_t)mnum < mthr;  // int vs uint compare
-            if (!skip) {
-                // KltoI3PMatrix + ProyI3Pto3PMatrix (global_tracker.cpp:553-570, ne10wrapper.h:414-424): P0 = (x z / zf, y z / zf, z),
-                // z = 1 / rho — from p_m and rho (16 B) instead of a stored P0 (24 B): one fp64 division for a third less traffic
-                const double sz = inv_mid(rho0);
-                const double pz_zf0 = a.inv_zfm * sz;
-                const double sx = pz_zf0 * (double)pm0.x, sy = pz_zf0 * (double)pm0.y;
-                const double *R = sq->Rt, *V = sq->Vt;
-                // Ne10::SE3on3PMatrix: dst = R(i,0)*x; dst += R(i,1)*y; dst += R(i,2)*z; dst = V + dst
-                ptx = R[0] * sx; ptx += R[1] * sy; ptx += R[2] * sz; ptx = V[0] + ptx;
-                pty = R[3] * sx; pty += R[4] * sy; pty += R[5] * sz; pty = V[1] + pty;
-                ptz = R[6] * sx; ptz += R[7] * sy; ptz += R[8] * sz; ptz = V[2] + ptz;
-                // Ne10::ProyP3toI3PMatrix
-                rho_p = inv_mid(ptz);
-                const double pz_zf = a.zfm * rho_p;
-                pix = pz_zf * ptx;
-                piy = pz_zf * pty;
-                const double px = pix + (double)a.ppx, py = piy + (double)a.ppy;  // cam_model::Hom2Img
-                const int x = cvt_trunc_sat_i32(px + 0.5), y = cvt_trunc_sat_i32(py + 0.5);   // (only the in-image test below looks at an out-of-range value)
-                // Huber weight k / |r| of the previous iteration's residual (global_tracker.cpp:370-372).  It multiplies the
-                // residual and the gradient, the uncertainty scaling q_rho = sqrt((s_rho w qvel)^2 + 1) divides them again
-                // (:452-463): together w / q_rho = 1 / sqrt((s_rho qvel)^2 + 1 / w^2), what EDGEHIP_TVR_REF_ORDER 0 computes.
-                dfx = 0; dfy = 0;
+    int mid_f = -1;
+    // status: 0 = skipped (no residual written), 1 = out of image (max_r), 2 = evaluated & matched (own fi),
+    //         3 = evaluated, unmatched (inherits the previous valid fi)
+    int status = 0;
+    double fi = 0;        // (every lane hands it to the shuffles below: it keeps its default)
+    double rho_own;       // the KeyLine's rho, kept for the key post of the last evaluation (no load behind the residual store); read with mid_f >= 0 only
+    if (ikl < kn) {
+        // Everything the KeyLine streams in is requested here, before the first use: the skip test, the projection, the
+        // in-image test and the two gathers are a chain of dependent memory round trips, and with the loads inside the
+        // branches each level of the chain paid its own.  (The ~10 % of KeyLines the tests drop load 36 B in vain.)
+        s_rho = ldg(ko.s_rho, ikl);
+        const int32_t mnum = ldg(ko.m_num, ikl);
+        const float2 pm0 = ldg(ko.p_m, ikl);
+        const double rho0 = ldg(ko.rho, ikl);
+        rho_own = rho0;
+        const float2 klm = ldg(ko.m_m, ikl);
+        const float knm = ldg(ko.n_m, ikl);
+        double rprev = 0;
+        if (REWEIGHT && !(ABL & 16)) rprev = rin[ikl];
+        const uint32_t fc = KF ? 0xFFFFFFFFu : a.framecount[seq];
+        const uint32_t mthr = a.match_num_thresh < fc ? a.match_num_thresh : fc;
+        const bool skip = s_rho > sq->s_rho_min_eval || (uint32_t)mnum < mthr;  // int vs uint compare
+        if (!skip) {
+            // KltoI3PMatrix + ProyI3Pto3PMatrix (global_tracker.cpp:553-570, ne10wrapper.h:414-424): P0 = (x z / zf, y z / zf, z),
+            // z = 1 / rho — from p_m and rho (16 B) instead of a stored P0 (24 B): one fp64 division for a third less traffic
+            const double sz = inv_mid(rho0);
+            const double pz_zf0 = a.inv_zfm * sz;
+            const double sx = pz_zf0 * (double)pm0.x, sy = pz_zf0 * (double)pm0.y;
+            const double *R = sq->Rt, *V = sq->Vt;
+            // Ne10::SE3on3PMatrix: dst = R(i,0)*x; dst += R(i,1)*y; dst += R(i,2)*z; dst = V + dst
+            ptx = R[0] * sx; ptx += R[1] * sy; ptx += R[2] * sz; ptx = V[0] + ptx;
+            pty = R[3] * sx; pty += R[4] * sy; pty += R[5] * sz; pty = V[1] + pty;
+            ptz = R[6] * sx; ptz += R[7] * sy; ptz += R[8] * sz; ptz = V[2] + ptz;
+            // Ne10::ProyP3toI3PMatrix
+            rho_p = inv_mid(ptz);
+            const double pz_zf = a.zfm * rho_p;
+            pix = pz_zf * ptx;
+            piy = pz_zf * pty;
+            const double px = pix + (double)a.ppx, py = piy + (double)a.ppy;  // cam_model::Hom2Img
+            const int x = cvt_trunc_sat_i32(px + 0.5), y = cvt_trunc_sat_i32(py + 0.5);   // (only the in-image test below looks at an out-of-range value)
+            // Huber weight k / |r| of the previous iteration's residual (global_tracker.cpp:370-372).  It multiplies the
+            // residual and the gradient, the uncertainty scaling q_rho = sqrt((s_rho w qvel)^2 + 1) divides them again
+            // (:452-463): together w / q_rho = 1 / sqrt((s_rho qvel)^2 + 1 / w^2), what EDGEHIP_TVR_REF_ORDER 0 computes.
+            dfx = 0; dfy = 0;
 #if EDGEHIP_TVR_REF_ORDER
-                wgt_ref = 1;
+            wgt_ref = 1;
 #endif
-                if (REWEIGHT) {
-                    if (is_carry(rprev)) rprev = carry_in_prev;
+            if (REWEIGHT) {
+                if (is_carry(rprev)) rprev = carry_in_prev;
 #if EDGEHIP_TVR_REF_ORDER
-                    if (fabs(rprev) > a.k_huber) wgt_ref = div_mid(a.k_huber, fabs(rprev));
+                if (fabs(rprev) > a.k_huber) wgt_ref = div_mid(a.k_huber, fabs(rprev));
 #else
-                    if (fabs(rprev) > a.k_huber && !(ABL & 2)) { const double rk = fabs(rprev) * a.inv_k_huber; inv_w2 = rk * rk; }
+                if (fabs(rprev) > a.k_huber && !(ABL & 2)) { const double rk = fabs(rprev) * a.inv_k_huber; inv_w2 = rk * rk; }
 #endif
-                }
-                fm = a.max_r;
-                if (x < 1 || y < 1 || x >= a.w - 1 || y >= a.h - 1) {
-                    status = 1;
-                } else {
-                    status = 3;
-                    // temporarily z-rotated gradient, stored back into a float Point2DF (:386-388)
-                    const float rmx = KF ? klm.x : (float)(sq->RM[0] * (double)klm.x + sq->RM[1] * (double)klm.y);
-                    const float rmy = KF ? klm.y : (float)(sq->RM[2] * (double)klm.x + sq->RM[3] * (double)klm.y);
-                    const uint32_t f = (ABL & 8) ? (uint32_t)(ikl + 1) : a.field16[(size_t)seq * a.f16stride + field16_index(x, y, a.f16tx)];
-                    if (KF) {
-                        if (f != 0u) {
-                            const int ikf = (int)f - 1;
-                            const KlSoA &kf = a.kl_new[seq];
-                            const MatchRec fr = kf.rec[ikf];
-                            const double f_rho = kf.rho[ikf], f_srho = kf.s_rho[ikf];
-                            // Calc_f_J_Complete (global_tracker.cpp:138-147): float products and quotients, compared in double
-                            const double cang = (double)((klm.x * fr.m_mx + klm.y * fr.m_my) / knm);
-                            const double rho_t = rho_p / a.kf[seq].Kr;          // PtIm[2*pnum+ikl]/Kr (kfvo.cpp:1481)
-                            const bool reject = cang < a.kf_match_cang || (double)fabsf(knm / fr.n_m - 1) > a.kf_match_mod ||
-                                                fabs(rho_t - f_rho) > a.kf_rho_tol * (f_srho + s_rho * rho_t / rho0);
-                            if (!reject) {
-                                const double dx = px - (double)fr.c_px, dy = py - (double)fr.c_py;
-                                fi = dx * (double)fr.u_mx + dy * (double)fr.u_my;
-                                dfx = (double)fr.u_mx;
-                                dfy = (double)fr.u_my;
-                                fm = fi;
-                                mid_f = ikf;
-                                status = 2;
-                            }
-                        }
-                    } else {
-                        // (an empty field entry reads record 0 and fails the test below by `f != 0`: one level of the nest less — each level costs
-                        // the moves of everything it may leave unchanged — and record 0's line is the same for every such lane)
-                        const int ikf = f != 0u ? (int)f - 1 : 0;
-                        // The matched KeyLine's c_p, m_m, u_m.  GREC: a 16-byte record (four records share the 64 bytes
-                        // a random gather moves, instead of two) and u_m recomputed with the detector's own float
-                        // expressions (k_emit; edge_finder.cpp:166-200), valid for KeyLines nothing has rotated since.
-                        float f_cpx, f_cpy, f_mx, f_my, f_ux, f_uy;
-                        if (ABL & 4) {
-                            f_cpx = (float)px; f_cpy = (float)py; f_mx = klm.x; f_my = klm.y; f_ux = 1.f; f_uy = 0.f;
-                        } else if (GREC) {
-                            const float4 g = ldg(a.kl_new[seq].grec, ikf);
-                            f_cpx = g.x; f_cpy = g.y; f_mx = g.z; f_my = g.w;
-                        } else {
-                            const MatchRec fr = a.kl_new[seq].rec[ikf];
-                            f_cpx = fr.c_px; f_cpy = fr.c_py; f_mx = fr.m_mx; f_my = fr.m_my; f_ux = fr.u_mx; f_uy = fr.u_my;
-                        }
-                        // Test_f_k (float arithmetic inside, compared in double)
-                        const double p_n2 = (double)(knm * knm);
-                        const double p_esc = (double)(rmx * f_mx + rmy * f_my);
-                        if ((f != 0u) & !(fabs(p_esc - p_n2) > a.match_thresh * p_n2)) {   // (`&`: one level, the record's load is not conditional)
-                            if (GREC) {
-                                const float n2m = f_mx * f_mx + f_my * f_my;
-                                const float nm = sqrtf_mid(n2m);
-                                div2_mid_f32(f_mx, f_my, nm, f_ux, f_uy);
-                            }
-                            const double dx = px - (double)f_cpx, dy = py - (double)f_cpy;
-                            fi = dx * (double)f_ux + dy * (double)f_uy;
-                            dfx = (double)f_ux;
-                            dfy = (double)f_uy;
+            }
+            fm = a.max_r;
+            if (x < 1 || y < 1 || x >= a.w - 1 || y >= a.h - 1) {
+                status = 1;
+            } else {
+                status = 3;
+                // temporarily z-rotated gradient, stored back into a float Point2DF (:386-388)
+                const float rmx = KF ? klm.x : (float)(sq->RM[0] * (double)klm.x + sq->RM[1] * (double)klm.y);
+                const float rmy = KF ? klm.y : (float)(sq->RM[2] * (double)klm.x + sq->RM[3] * (double)klm.y);
+                const uint32_t f = (ABL & 8) ? (uint32_t)(ikl + 1) : a.field16[(size_t)seq * a.f16stride + field16_index(x, y, a.f16tx)];
+                if (KF) {
+                    if (f != 0u) {
+                        const int ikf = (int)f - 1;
+                        const KlSoA &kf = a.kl_new[seq];
+                        const MatchRec fr = kf.rec[ikf];
+                        const double f_rho = kf.rho[ikf], f_srho = kf.s_rho[ikf];
+                        // Calc_f_J_Complete (global_tracker.cpp:138-147): float products and quotients, compared in double
+                        const double cang = (double)((klm.x * fr.m_mx + klm.y * fr.m_my) / knm);
+                        const double rho_t = rho_p / a.kf[seq].Kr;          // PtIm[2*pnum+ikl]/Kr (kfvo.cpp:1481)
+                        const bool reject = cang < a.kf_match_cang || (double)fabsf(knm / fr.n_m - 1) > a.kf_match_mod ||
+                                            fabs(rho_t - f_rho) > a.kf_rho_tol * (f_srho + s_rho * rho_t / rho0);
+                        if (!reject) {
+                            const double dx = px - (double)fr.c_px, dy = py - (double)fr.c_py;
+                            fi = dx * (double)fr.u_mx + dy * (double)fr.u_my;
+                            dfx = (double)fr.u_mx;
+                            dfy = (double)fr.u_my;
                             fm = fi;
                             mid_f = ikf;
                             status = 2;
                         }
                     }
+                } else {
+                    // (an empty field entry reads record 0 and fails the test below by `f != 0`: one level of the nest less — each level costs
+                    // the moves of everything it may leave unchanged — and record 0's line is the same for every such lane)
+                    const int ikf = f != 0u ? (int)f - 1 : 0;
+                    float f_cpx, f_cpy, f_mx, f_my, f_ux, f_uy;
+                    if (ABL & 4) {
+                        f_cpx = (float)px; f_cpy = (float)py; f_mx = klm.x; f_my = klm.y; f_ux = 1.f; f_uy = 0.f;
+                    } else {
+                        load_matched<GREC>(a.kl_new[seq], ikf, f_cpx, f_cpy, f_mx, f_my, f_ux, f_uy);
+                    }
+                    // Test_f_k (float arithmetic inside, compared in double)
+                    const double p_n2 = (double)(knm * knm);
+                    const double p_esc = (double)(rmx * f_mx + rmy * f_my);
+                    if ((f != 0u) & !(fabs(p_esc - p_n2) > a.match_thresh * p_n2)) {   // (`&`: one level, the record's load is not conditional)
+                        if (GREC) grec_u_m(f_mx, f_my, f_ux, f_uy);
+                        const double dx = px - (double)f_cpx, dy = py - (double)f_cpy;
+                        fi = dx * (double)f_ux + dy * (double)f_uy;
+                        dfx = (double)f_ux;
+                        dfy = (double)f_uy;
+                        fm = fi;
+                        mid_f = ikf;
+                        status = 2;
+                    }
                 }
             }
         }
+    }
 
-        // ---- DResidualNew: "last valid fi" propagation (KeyLine order = pass, wave, lane) ----
-        {
-            const unsigned long long vmask = __ballot(status == 2);
-            const unsigned long long below = vmask & ((1ull << lane) - 1ull);
-            const int src = below ? 63 - __clzll(below) : 0;
-            const double inh = __shfl(fi, src, 64);
-            const int top = vmask ? 63 - __clzll(vmask) : 0;
-            const double wl = __shfl(fi, top, 64);
-            if (lane == 0) {
-                s_whas[pass][wave] = vmask != 0;
-                s_wlast[pass][wave] = wl;
-            }
-            __syncthreads();   // entries of earlier passes were published by earlier barriers
-            if (status == 3) {
-                double v = marker;   // no valid KeyLine before this one inside the block: resolved from the block carries
-                bool have = false;
-                if (below) { v = inh; have = true; }
-                for (int pp = pass; pp >= 0 && !have; pp--)
-                    for (int pw = (pp == pass ? wave - 1 : NW - 1); pw >= 0 && !have; pw--)
-                        if (s_whas[pp][pw]) { v = s_wlast[pp][pw]; have = true; }
-                rout[ikl] = v;
-            } else if (status == 2) {
-                rout[ikl] = fi;
-            } else if (status == 1) {
-                rout[ikl] = a.max_r;
-            } else if (ikl < kn) {
-                // a KeyLine the gates skip (the same ones in every evaluation of a minimisation): the reference leaves its entry
-                // alone and nothing ever reads it; it is written anyway so that the wave stores whole lines (with ~13 % of the
-                // lanes masked most lines would be written in part, which the memory system turns into read-modify-write)
-                rout[ikl] = 0.0;
-            }
+    // ---- DResidualNew: "last valid fi" propagation (resid_carry.h; KeyLine order = wave, lane) ----
+    {
+        const WaveLast<double> wl = wave_last_valid(fi, status == 2, lane);
+        carry_publish(wl, lane, wave, s_wlast, s_whas);
+        __syncthreads();
+        if (status == 3) {
+            rout[ikl] = carry_inherit(wl, wave, s_wlast, s_whas);
+        } else if (status == 2) {
+            rout[ikl] = fi;
+        } else if (status == 1) {
+            rout[ikl] = a.max_r;
+        } else if (ikl < kn) {
+            rout[ikl] = 0.0;   // a KeyLine the gates skip: whole-line stores
         }
-        if (a.write_mid && ikl < kn) {
-            stg(ko.m_id_f, ikl, mid_f);   // (a global store: the FLAT one also counts on the LDS counter, ctx.h)
-            if (!KF && a.fwd_key && mid_f >= 0) atomicMax(&a.fwd_key[(size_t)seq * a.cap + mid_f], ord_bits(rho_own));
-        }
+    }
+    if (a.write_mid && ikl < kn) {
+        stg(ko.m_id_f, ikl, mid_f);   // (a global store: the FLAT one also counts on the LDS counter, ctx.h)
+        if (!KF && a.fwd_key && mid_f >= 0) atomicMax(&a.fwd_key[(size_t)seq * a.cap + mid_f], ord_bits(rho_own));
+    }
 
-        // ---- Jacobian row, uncertainty scaling (global_tracker.cpp:419-463) ----
-        double fs = 0;   // the scaled residual: the row's seventh value (zero, like J, for a KeyLine that was not evaluated)
-        if (status != 0) {
+    // ---- Jacobian row, uncertainty scaling (global_tracker.cpp:419-463) ----
+    double fs = 0;   // the scaled residual: the row's seventh value (zero, like J, for a KeyLine that was not evaluated)
+    if (status != 0) {
 #if EDGEHIP_TVR_REF_ORDER
-            if (REWEIGHT) { fm *= wgt_ref; dfx *= wgt_ref; dfy *= wgt_ref; }
+        if (REWEIGHT) { fm *= wgt_ref; dfx *= wgt_ref; dfy *= wgt_ref; }
 #endif
-            if (PROCJF) {
-                double t0 = a.zfm * rho_p;
-                J[0] = t0 * dfx;
-                J[1] = t0 * dfy;
-                t0 = rho_p * pix;
-                J[2] = t0 * dfx;
-                t0 = rho_p * piy;
-                J[2] += t0 * dfy;
-                J[3] = J[1] * ptz; J[3] += J[2] * pty;
-                J[4] = J[0] * ptz; J[4] += J[2] * ptx;
-                t0 = J[0] * pty;
-                J[5] = -1 * t0; J[5] += J[1] * ptx;
-            }
-            const double qvel = (a.zfm * dfx * sq->Vt[0] + a.zfm * dfy * sq->Vt[1] + (pix * dfx + piy * dfy) * sq->Vt[2]);
-            // the reference divides the seven values by q_rho one by one (EDGEHIP_TVR_REF_ORDER above; with 0 qvel is the unweighted one)
+        if (PROCJF) jac_row(J, a.zfm, rho_p, pix, piy, ptx, pty, ptz, dfx, dfy);
+        const double qvel = (a.zfm * dfx * sq->Vt[0] + a.zfm * dfy * sq->Vt[1] + (pix * dfx + piy * dfy) * sq->Vt[2]);
+        // the reference divides the seven values by q_rho one by one (EDGEHIP_TVR_REF_ORDER above; with 0 qvel is the unweighted one)
 #if EDGEHIP_TVR_REF_ORDER
-            const double q_rho = REWEIGHT ? sqrt_ge1(s_rho * qvel * s_rho * qvel + 1) : s_rho;
-            const double r_q = rcp_for_div_rn(q_rho);
-            if (PROCJF) {
+        const double q_rho = REWEIGHT ? sqrt_ge1(s_rho * qvel * s_rho * qvel + 1) : s_rho;
+        const double r_q = rcp_for_div_rn(q_rho);
+        if (PROCJF) {
 #pragma unroll
-                for (int j = 0; j < 6; j++) J[j] = div_rn(J[j], q_rho, r_q);
-            }
-            fs = div_rn(fm, q_rho, r_q);
+            for (int j = 0; j < 6; j++) J[j] = div_rn(J[j], q_rho, r_q);
+        }
+        fs = div_rn(fm, q_rho, r_q);
 #else
-            double inv_q;
-            if (REWEIGHT) {
-                const double sq = s_rho * qvel;
-                inv_q = (ABL & 2) ? sq + inv_w2 : rsqrt_f64(sq * sq + inv_w2);
-            } else {
-                inv_q = 1.0 / s_rho;
-            }
-            if (PROCJF) {
-#pragma unroll
-                for (int j = 0; j < 6; j++) J[j] *= inv_q;
-            }
-            fs = fm * inv_q;
-#endif
-        } else if (!REWEIGHT && !KF && ikl < kn && s_rho == 0) {
-            // (as in tvr2_body: the reference's 0 / 0 for a skipped KeyLine with s_rho = 0, global_tracker.cpp:456-461, :507)
-            const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-            if (PROCJF) {
-#pragma unroll
-                for (int j = 0; j < 6; j++) J[j] = qnan;
-            }
-            fs = qnan;
-        }
-        if (GRAM_MFMA) {
-            // the KeyLine's row (J0..J5, fm, 0) for the Gram matrix below; rows of skipped / absent KeyLines are zero
-            double2 *row = reinterpret_cast<double2 *>(&s_rows[wave][lane][0]);
-            row[0] = make_double2(J[0], J[1]);
-            row[1] = make_double2(J[2], J[3]);
-            row[2] = make_double2(J[4], J[5]);
-            row[3] = make_double2(fs, 0.0);
+        double inv_q;
+        if (REWEIGHT) {
+            const double sq = s_rho * qvel;
+            inv_q = (ABL & 2) ? sq + inv_w2 : rsqrt_f64(sq * sq + inv_w2);
         } else {
-            int ns = 0;
-            if (PROCJF) {
-#pragma unroll
-                // (one KeyLine per thread: the product IS the lane's term — `0.0 + product` would cost an add per sum, 28 of the evaluation's ~600
-                // vector instructions, to turn a -0.0 product into +0.0, which the reference's PairWiseVAdd over the bare products does not do either)
-                for (int i = 0; i < 6; i++)
-#pragma unroll
-                    for (int j = i; j < 6; j++) { const double pr = J[i] * J[j]; sums[ns] = kTvrPasses == 1 ? pr : sums[ns] + pr; ns++; }
-#pragma unroll
-                for (int i = 0; i < 6; i++) { const double pr = J[i] * fs; sums[ns] = kTvrPasses == 1 ? pr : sums[ns] + pr; ns++; }
-            }
-            { const double pr = fs * fs; const int at = PROCJF ? ns : kNumSums - 1; sums[at] = kTvrPasses == 1 ? pr : sums[at] + pr; }
+            inv_q = 1.0 / s_rho;
         }
+        if (PROCJF) {
+#pragma unroll
+            for (int j = 0; j < 6; j++) J[j] *= inv_q;
+        }
+        fs = fm * inv_q;
+#endif
+    } else if (!REWEIGHT && !KF && ikl < kn && s_rho == 0) {
+        // (as in tvr2_body: the reference's 0 / 0 for a skipped KeyLine with s_rho = 0, global_tracker.cpp:456-461, :507)
+        const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+        if (PROCJF) {
+#pragma unroll
+            for (int j = 0; j < 6; j++) J[j] = qnan;
+        }
+        fs = qnan;
+    }
+    if (GRAM_MFMA) {
+        // the KeyLine's row (J0..J5, fm, 0) for the Gram matrix below; rows of skipped / absent KeyLines are zero
+        double2 *row = reinterpret_cast<double2 *>(&s_rows[wave][lane][0]);
+        row[0] = make_double2(J[0], J[1]);
+        row[1] = make_double2(J[2], J[3]);
+        row[2] = make_double2(J[4], J[5]);
+        row[3] = make_double2(fs, 0.0);
+    } else {
+        int ns = 0;
+        if (PROCJF) {
+#pragma unroll
+            // (one KeyLine per thread: the product IS the lane's term — `0.0 + product` would cost an add per sum, 28 of the evaluation's ~600
+            // vector instructions, to turn a -0.0 product into +0.0, which the reference's PairWiseVAdd over the bare products does not do either)
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int j = i; j < 6; j++) sums[ns++] = J[i] * J[j];
+#pragma unroll
+            for (int i = 0; i < 6; i++) sums[ns++] = J[i] * fs;
+        }
+        sums[PROCJF ? ns : kNumSums - 1] = fs * fs;
     }
 
-    // last valid fi of the whole block (marker if none), for the carries of the following blocks
-    if (tid == 0) {
-        double bl = marker;
-        for (int pp = kTvrPasses - 1; pp >= 0 && is_carry(bl); pp--) {
-            if (blk * kTvrBlock + pp * kTvrThreads >= kn) continue;
-            for (int pw = NW - 1; pw >= 0; pw--)
-                if (s_whas[pp][pw]) { bl = s_wlast[pp][pw]; break; }
-        }
-        a.block_last[(size_t)seq * a.nblk + blk] = bl;
-    }
+    if (tid == 0) a.block_last[(size_t)seq * a.nblk + blk] = carry_block_last(s_wlast, s_whas);
 
     // ---- block reduction: transposed (halving) wave reduction, LDS across waves, one partial per block ----
     __shared__ double s_red[NW][32];
@@ -1122,22 +1099,11 @@ __device__ __forceinline__ void tvr_body(const TvrArgs &a, const int seq, const 
         }
     } else if (PROCJF && (ABL & 1)) {
         if (lane < kNumSums) s_red[wave][lane] = sums[lane % 4];
-    } else if (PROCJF) {
-        const int idx = wave_reduce28(sums, lane);
-        if ((lane & 1) == 0) s_red[wave][idx] = sums[0];
     } else {
-        double v = sums[kNumSums - 1];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) s_red[wave][kNumSums - 1] = v;
+        block_reduce_put<PROCJF>(sums, lane, wave, s_red);
     }
     __syncthreads();
-    if (PROCJF ? tid < kNumSums : tid == kNumSums - 1) {
-        double v = s_red[0][tid];
-#pragma unroll
-        for (int wv = 1; wv < NW; wv++) v += s_red[wv][tid];   // fixed order: deterministic
-        a.partials[((size_t)seq * a.nblk + blk) * kNumSums + tid] = v;
-    }
+    block_reduce_store<PROCJF>(s_red, tid, a.partials + ((size_t)seq * a.nblk + blk) * kNumSums);
 }
 
 template <bool REWEIGHT, bool PROCJF, bool GREC>
@@ -1165,7 +1131,6 @@ __global__ __launch_bounds__(kTvrThreads) void k_try_velrot_kf(TvrArgs a) {
 // ---------------------------------------------------------------------------------------------------
 template <bool REWEIGHT, bool PROCJF, bool GREC>
 __device__ __forceinline__ void tvr_body_f32(const TvrArgs &a, const int seq, const int blk, const int tid) {
-    static_assert(kTvrPasses == 1, "one KeyLine per thread");
     const int lane = tid & 63, wave = tid >> 6;
     SeqDev *sq = a.seq + seq;
     const int kn = a.kn_old[seq];
@@ -1175,7 +1140,6 @@ __device__ __forceinline__ void tvr_body_f32(const TvrArgs &a, const int seq, co
     const double *rin = a.resid + ((size_t)res_in * a.nseq + seq) * a.cap;
     double *rout = a.resid + ((size_t)res_out * a.nseq + seq) * a.cap;
     const double carry_in_prev = a.resid_carry[((size_t)res_in * a.nseq + seq) * a.nblk + blk];
-    const double marker = __longlong_as_double((long long)resid_carry_bits());
     constexpr int NW = kTvrThreads / 64;
     __shared__ float s_wlast[NW];
     __shared__ int s_whas[NW];
@@ -1242,21 +1206,11 @@ __device__ __forceinline__ void tvr_body_f32(const TvrArgs &a, const int seq, co
                 {
                     const int ikf = f != 0u ? (int)f - 1 : 0;   // (an empty entry reads record 0 and fails by `f != 0` below: tvr_body)
                     float f_cpx, f_cpy, f_mx, f_my, f_ux, f_uy;
-                    if (GREC) {
-                        const float4 g = ldg(a.kl_new[seq].grec, ikf);
-                        f_cpx = g.x; f_cpy = g.y; f_mx = g.z; f_my = g.w;
-                    } else {
-                        const MatchRec fr = a.kl_new[seq].rec[ikf];
-                        f_cpx = fr.c_px; f_cpy = fr.c_py; f_mx = fr.m_mx; f_my = fr.m_my; f_ux = fr.u_mx; f_uy = fr.u_my;
-                    }
+                    load_matched<GREC>(a.kl_new[seq], ikf, f_cpx, f_cpy, f_mx, f_my, f_ux, f_uy);
                     const float p_n2 = knm * knm;                      // Test_f_k<float> (global_tracker.h:90-104)
                     const float p_esc = rmx * f_mx + rmy * f_my;
                     if ((f != 0u) & !(fabsf(p_esc - p_n2) > simil_t * p_n2)) {
-                        if (GREC) {
-                            const float n2m = f_mx * f_mx + f_my * f_my;
-                            const float nm = sqrtf_mid(n2m);
-                            div2_mid_f32(f_mx, f_my, nm, f_ux, f_uy);
-                        }
+                        if (GREC) grec_u_m(f_mx, f_my, f_ux, f_uy);
                         const float dx = px - f_cpx, dy = py - f_cpy;    // Calc_f_J2<float> (global_tracker.cpp:228-271)
                         fi = dx * f_ux + dy * f_uy;
                         dfx = f_ux;
@@ -1269,26 +1223,13 @@ __device__ __forceinline__ void tvr_body_f32(const TvrArgs &a, const int seq, co
             }
         }
     }
-    // ---- DResidualNew: "last valid fi" propagation (KeyLine order = wave, lane), as in tvr_body ----
+    // ---- DResidualNew: "last valid fi" propagation (resid_carry.h), float values widened at the store ----
     {
-        const unsigned long long vmask = __ballot(status == 2);
-        const unsigned long long below = vmask & ((1ull << lane) - 1ull);
-        const int src = below ? 63 - __clzll(below) : 0;
-        const float inh = __shfl(fi, src, 64);
-        const int top = vmask ? 63 - __clzll(vmask) : 0;
-        const float wl = __shfl(fi, top, 64);
-        if (lane == 0) {
-            s_whas[wave] = vmask != 0;
-            s_wlast[wave] = wl;
-        }
+        const WaveLast<float> wl = wave_last_valid(fi, status == 2, lane);
+        carry_publish(wl, lane, wave, s_wlast, s_whas);
         __syncthreads();
         if (status == 3) {
-            double v = marker;
-            bool have = false;
-            if (below) { v = (double)inh; have = true; }
-            for (int pw = wave - 1; pw >= 0 && !have; pw--)
-                if (s_whas[pw]) { v = (double)s_wlast[pw]; have = true; }
-            rout[ikl] = v;
+            rout[ikl] = carry_inherit(wl, wave, s_wlast, s_whas);
         } else if (status == 2) {
             rout[ikl] = (double)fi;
         } else if (status == 1) {
@@ -1305,19 +1246,7 @@ __device__ __forceinline__ void tvr_body_f32(const TvrArgs &a, const int seq, co
     float fs = 0.f;   // the scaled residual (zero, like J, for a KeyLine that was not evaluated)
     if (status != 0) {
         if (REWEIGHT) { fm *= wgt; dfx *= wgt; dfy *= wgt; }
-        if (PROCJF) {
-            float t0 = zf * rho_p;
-            J[0] = t0 * dfx;
-            J[1] = t0 * dfy;
-            t0 = rho_p * pix;
-            J[2] = t0 * dfx;
-            t0 = rho_p * piy;
-            J[2] += t0 * dfy;
-            J[3] = J[1] * ptz; J[3] += J[2] * pty;
-            J[4] = J[0] * ptz; J[4] += J[2] * ptx;
-            t0 = J[0] * pty;
-            J[5] = -1.f * t0; J[5] += J[1] * ptx;
-        }
+        if (PROCJF) jac_row(J, zf, rho_p, pix, piy, ptx, pty, ptz, dfx, dfy);
         // qvel: a float expression (zfm, the derivatives, PtIm and Vt are floats) assigned to a double (:452-453); q_rho in double
         const double qvel = (double)(zf * dfx * Vt0 + zf * dfy * Vt1 + (pix * dfx + piy * dfy) * Vt2);
         const double q_rho = REWEIGHT ? sqrt_ge1(s_rho * qvel * s_rho * qvel + 1) : s_rho;
@@ -1340,29 +1269,12 @@ __device__ __forceinline__ void tvr_body_f32(const TvrArgs &a, const int seq, co
         }
         sums[PROCJF ? ns : kNumSums - 1] = fs * fs;
     }
-    if (tid == 0) {
-        double bl = marker;
-        for (int pw = NW - 1; pw >= 0; pw--)
-            if (s_whas[pw]) { bl = (double)s_wlast[pw]; break; }
-        a.block_last[(size_t)seq * a.nblk + blk] = bl;
-    }
+    if (tid == 0) a.block_last[(size_t)seq * a.nblk + blk] = carry_block_last(s_wlast, s_whas);
     __shared__ float s_red[NW][32];
-    if (PROCJF) {
-        const int idx = wave_reduce28_f32(sums, lane);
-        if ((lane & 1) == 0) s_red[wave][idx] = sums[0];
-    } else {
-        float v = sums[kNumSums - 1];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) s_red[wave][kNumSums - 1] = v;
-    }
+    // (float sums widened at the store: the step kernel adds the blocks' sums in double and rounds to float)
+    block_reduce_put<PROCJF>(sums, lane, wave, s_red);
     __syncthreads();
-    if (PROCJF ? tid < kNumSums : tid == kNumSums - 1) {
-        float v = s_red[0][tid];
-#pragma unroll
-        for (int wv = 1; wv < NW; wv++) v += s_red[wv][tid];
-        a.partials[((size_t)seq * a.nblk + blk) * kNumSums + tid] = (double)v;   // the step kernel adds the blocks' sums (in double) and rounds to float
-    }
+    block_reduce_store<PROCJF>(s_red, tid, a.partials + ((size_t)seq * a.nblk + blk) * kNumSums);
 }
 template <bool REWEIGHT, bool PROCJF, bool GREC>
 __global__ __launch_bounds__(kTvrThreads) void k_try_velrot_f32(TvrArgs a) {
@@ -1392,11 +1304,9 @@ __device__ __forceinline__ void tvr2_body(const TvrArgs &a, const int seq, const
     SeqDev *sq = a.seq + seq;
     const int kn = a.kn_old[seq];
     if (blk * kTvrBlock >= kn) return;  // whole block beyond the list (block-uniform)
-    static_assert(kTvrPasses == 1, "one KeyLine per thread");
     const KlSoA &ko = a.kl_old[seq];
     double *rout0 = a.resid + ((size_t)sq->res_t * a.nseq + seq) * a.cap;
     double *rout1 = a.resid + ((size_t)sq->res_new * a.nseq + seq) * a.cap;
-    const double marker = __longlong_as_double((long long)resid_carry_bits());
     constexpr int NW = kTvrThreads / 64;
     __shared__ double s_wlast[2][NW];
     __shared__ int s_whas[2][NW];
@@ -1406,7 +1316,7 @@ __device__ __forceinline__ void tvr2_body(const TvrArgs &a, const int seq, const
     // (no defaults for what only an evaluated KeyLine — status != 0 — reads in the Jacobian section: see tvr_body)
     double fm[2], dfx[2], dfy[2], fi[2] = {0, 0};
     double ptx[2], pty[2], ptz[2], pix[2], piy[2], rho_p[2];
-    int status[2] = {0, 0};   // 0 skipped, 1 out of image, 2 matched, 3 evaluated and unmatched (tvr_body)
+    int status[2] = {0, 0};   // 0 skipped, 1 out of image, 2 matched, 3 evaluated and unmatched (resid_carry.h)
     double s_rho = 1;
     if (ikl < kn) {
         s_rho = ldg(ko.s_rho, ikl);
@@ -1453,15 +1363,8 @@ __device__ __forceinline__ void tvr2_body(const TvrArgs &a, const int seq, const
             const bool hit0 = inimg[0] && f0 != 0u, hit1 = inimg[1] && f1 != 0u;
             const int ikf0 = hit0 ? (int)f0 - 1 : 0, ikf1 = hit1 ? (int)f1 - 1 : 0;
             float f_cpx[2], f_cpy[2], f_mx[2], f_my[2], f_ux[2] = {0, 0}, f_uy[2] = {0, 0};
-            if (GREC) {
-                const float4 g0 = ldg(a.kl_new[seq].grec, ikf0), g1 = ldg(a.kl_new[seq].grec, ikf1);
-                f_cpx[0] = g0.x; f_cpy[0] = g0.y; f_mx[0] = g0.z; f_my[0] = g0.w;
-                f_cpx[1] = g1.x; f_cpy[1] = g1.y; f_mx[1] = g1.z; f_my[1] = g1.w;
-            } else {
-                const MatchRec r0 = a.kl_new[seq].rec[ikf0], r1 = a.kl_new[seq].rec[ikf1];
-                f_cpx[0] = r0.c_px; f_cpy[0] = r0.c_py; f_mx[0] = r0.m_mx; f_my[0] = r0.m_my; f_ux[0] = r0.u_mx; f_uy[0] = r0.u_my;
-                f_cpx[1] = r1.c_px; f_cpy[1] = r1.c_py; f_mx[1] = r1.m_mx; f_my[1] = r1.m_my; f_ux[1] = r1.u_mx; f_uy[1] = r1.u_my;
-            }
+            load_matched<GREC>(a.kl_new[seq], ikf0, f_cpx[0], f_cpy[0], f_mx[0], f_my[0], f_ux[0], f_uy[0]);
+            load_matched<GREC>(a.kl_new[seq], ikf1, f_cpx[1], f_cpy[1], f_mx[1], f_my[1], f_ux[1], f_uy[1]);
             const double p_n2 = (double)(knm * knm);
 #pragma unroll
             for (int c = 0; c < 2; c++) {
@@ -1469,11 +1372,7 @@ __device__ __forceinline__ void tvr2_body(const TvrArgs &a, const int seq, const
                     // Test_f_k (float arithmetic inside, compared in double); `&`: one level of the nest for the hit and the test (tvr_body)
                     const double p_esc = (double)(rmx[c] * f_mx[c] + rmy[c] * f_my[c]);
                     if ((c ? hit1 : hit0) & !(fabs(p_esc - p_n2) > a.match_thresh * p_n2)) {
-                        if (GREC) {
-                            const float n2m = f_mx[c] * f_mx[c] + f_my[c] * f_my[c];
-                            const float nm = sqrtf_mid(n2m);
-                            div2_mid_f32(f_mx[c], f_my[c], nm, f_ux[c], f_uy[c]);
-                        }
+                        if (GREC) grec_u_m(f_mx[c], f_my[c], f_ux[c], f_uy[c]);
                         const double dx = px[c] - (double)f_cpx[c], dy = py[c] - (double)f_cpy[c];
                         fi[c] = dx * (double)f_ux[c] + dy * (double)f_uy[c];
                         dfx[c] = (double)f_ux[c];
@@ -1486,49 +1385,31 @@ __device__ __forceinline__ void tvr2_body(const TvrArgs &a, const int seq, const
         }
     }
 
-    // ---- DResidualNew of both chains: "last valid fi" propagation (KeyLine order = wave, lane), one barrier for the two ----
-    unsigned long long below[2];
-    double inh[2];
+    // ---- DResidualNew of both chains: "last valid fi" propagation (resid_carry.h), one barrier for the two ----
+    WaveLast<double> wl[2];
 #pragma unroll
     for (int c = 0; c < 2; c++) {
-        const unsigned long long vmask = __ballot(status[c] == 2);
-        below[c] = vmask & ((1ull << lane) - 1ull);
-        const int src = below[c] ? 63 - __clzll(below[c]) : 0;
-        inh[c] = __shfl(fi[c], src, 64);
-        const int top = vmask ? 63 - __clzll(vmask) : 0;
-        const double wl = __shfl(fi[c], top, 64);
-        if (lane == 0) {
-            s_whas[c][wave] = vmask != 0;
-            s_wlast[c][wave] = wl;
-        }
+        wl[c] = wave_last_valid(fi[c], status[c] == 2, lane);
+        carry_publish(wl[c], lane, wave, s_wlast[c], s_whas[c]);
     }
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < 2; c++) {
         double *rout = c ? rout1 : rout0;
         if (status[c] == 3) {
-            double v = marker;   // no valid KeyLine before this one inside the block: resolved from the block carries
-            bool have = false;
-            if (below[c]) { v = inh[c]; have = true; }
-            for (int pw = wave - 1; pw >= 0 && !have; pw--)
-                if (s_whas[c][pw]) { v = s_wlast[c][pw]; have = true; }
-            rout[ikl] = v;
+            rout[ikl] = carry_inherit(wl[c], wave, s_wlast[c], s_whas[c]);
         } else if (status[c] == 2) {
             rout[ikl] = fi[c];
         } else if (status[c] == 1) {
             rout[ikl] = a.max_r;
         } else if (ikl < kn) {
-            rout[ikl] = 0.0;   // a KeyLine the gates skip: whole-line stores (tvr_body)
+            rout[ikl] = 0.0;   // a KeyLine the gates skip: whole-line stores
         }
     }
     if (tid == 0) {
 #pragma unroll
-        for (int c = 0; c < 2; c++) {
-            double bl = marker;
-            for (int pw = NW - 1; pw >= 0; pw--)
-                if (s_whas[c][pw]) { bl = s_wlast[c][pw]; break; }
-            (c ? a.block_last : a.block_last_z)[(size_t)seq * a.nblk + blk] = bl;
-        }
+        for (int c = 0; c < 2; c++)
+            (c ? a.block_last : a.block_last_z)[(size_t)seq * a.nblk + blk] = carry_block_last(s_wlast[c], s_whas[c]);
     }
 
     // ---- Jacobian rows, uncertainty scaling, the 28 sums: chain by chain ----
@@ -1543,24 +1424,14 @@ __device__ __forceinline__ void tvr2_body(const TvrArgs &a, const int seq, const
     double Jc[2][6], fmc[2];
 #pragma unroll
     for (int c = 0; c < 2; c++) {
-        double *J = Jc[c];
+        double (&J)[6] = Jc[c];
 #pragma unroll
         for (int j = 0; j < 6; j++) J[j] = 0;
         fmc[c] = 0;
         if (status[c] != 0) {   // (a skipped KeyLine's row is exact zeros)
             fmc[c] = fm[c];
             if (PROCJF) {
-                double t0 = a.zfm * rho_p[c];
-                J[0] = t0 * dfx[c];
-                J[1] = t0 * dfy[c];
-                t0 = rho_p[c] * pix[c];
-                J[2] = t0 * dfx[c];
-                t0 = rho_p[c] * piy[c];
-                J[2] += t0 * dfy[c];
-                J[3] = J[1] * ptz[c]; J[3] += J[2] * pty[c];
-                J[4] = J[0] * ptz[c]; J[4] += J[2] * ptx[c];
-                t0 = J[0] * pty[c];
-                J[5] = -1 * t0; J[5] += J[1] * ptx[c];
+                jac_row(J, a.zfm, rho_p[c], pix[c], piy[c], ptx[c], pty[c], ptz[c], dfx[c], dfy[c]);
 #if EDGEHIP_TVR_REF_ORDER
 #pragma unroll
                 for (int j = 0; j < 6; j++) J[j] = div_rn(J[j], s_rho, inv_q);   // the reference's seven quotients (see div_rn)
@@ -1617,25 +1488,16 @@ __device__ __forceinline__ void tvr2_body(const TvrArgs &a, const int seq, const
 #pragma unroll
             for (int i = 0; i < 6; i++) sums[ns++] = J[i] * f;
             sums[ns] = f * f;
-            const int idx = wave_reduce28(sums, lane);
-            if ((lane & 1) == 0) s_red[c][wave][idx] = sums[0];
+            block_reduce_put<true>(sums, lane, wave, s_red[c]);
         } else {
-            double v = fmc[c] * fmc[c];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if (lane == 0) s_red[c][wave][kNumSums - 1] = v;
+            block_reduce_put_score(fmc[c] * fmc[c], lane, wave, s_red[c]);
         }
     }
     __syncthreads();
-    // wave 0 finishes chain 1, wave 1 chain 0 (fixed order over the block's waves: deterministic)
+    // wave 0 finishes chain 1, wave 1 chain 0
     if (wave < 2) {
         const int c = 1 - wave;
-        if (PROCJF ? lane < kNumSums : lane == kNumSums - 1) {
-            double v = s_red[c][0][lane];
-#pragma unroll
-            for (int wv = 1; wv < NW; wv++) v += s_red[c][wv][lane];
-            (c ? a.partials : a.partials_z)[((size_t)seq * a.nblk + blk) * kNumSums + lane] = v;
-        }
+        block_reduce_store<PROCJF>(s_red[c], lane, (c ? a.partials : a.partials_z) + ((size_t)seq * a.nblk + blk) * kNumSums);
     }
 }
 
@@ -1648,11 +1510,9 @@ __device__ __forceinline__ void tvr2_body_f32(const TvrArgs &a, const int seq, c
     SeqDev *sq = a.seq + seq;
     const int kn = a.kn_old[seq];
     if (blk * kTvrBlock >= kn) return;
-    static_assert(kTvrPasses == 1, "one KeyLine per thread");
     const KlSoA &ko = a.kl_old[seq];
     double *rout0 = a.resid + ((size_t)sq->res_t * a.nseq + seq) * a.cap;
     double *rout1 = a.resid + ((size_t)sq->res_new * a.nseq + seq) * a.cap;
-    const double marker = __longlong_as_double((long long)resid_carry_bits());
     constexpr int NW = kTvrThreads / 64;
     __shared__ float s_wlast[2][NW];
     __shared__ int s_whas[2][NW];
@@ -1706,26 +1566,15 @@ __device__ __forceinline__ void tvr2_body_f32(const TvrArgs &a, const int seq, c
             const bool hit0 = inimg[0] && f0 != 0u, hit1 = inimg[1] && f1 != 0u;
             const int ikf0 = hit0 ? (int)f0 - 1 : 0, ikf1 = hit1 ? (int)f1 - 1 : 0;
             float f_cpx[2], f_cpy[2], f_mx[2], f_my[2], f_ux[2] = {0, 0}, f_uy[2] = {0, 0};
-            if (GREC) {
-                const float4 g0 = ldg(a.kl_new[seq].grec, ikf0), g1 = ldg(a.kl_new[seq].grec, ikf1);
-                f_cpx[0] = g0.x; f_cpy[0] = g0.y; f_mx[0] = g0.z; f_my[0] = g0.w;
-                f_cpx[1] = g1.x; f_cpy[1] = g1.y; f_mx[1] = g1.z; f_my[1] = g1.w;
-            } else {
-                const MatchRec r0 = a.kl_new[seq].rec[ikf0], r1 = a.kl_new[seq].rec[ikf1];
-                f_cpx[0] = r0.c_px; f_cpy[0] = r0.c_py; f_mx[0] = r0.m_mx; f_my[0] = r0.m_my; f_ux[0] = r0.u_mx; f_uy[0] = r0.u_my;
-                f_cpx[1] = r1.c_px; f_cpy[1] = r1.c_py; f_mx[1] = r1.m_mx; f_my[1] = r1.m_my; f_ux[1] = r1.u_mx; f_uy[1] = r1.u_my;
-            }
+            load_matched<GREC>(a.kl_new[seq], ikf0, f_cpx[0], f_cpy[0], f_mx[0], f_my[0], f_ux[0], f_uy[0]);
+            load_matched<GREC>(a.kl_new[seq], ikf1, f_cpx[1], f_cpy[1], f_mx[1], f_my[1], f_ux[1], f_uy[1]);
             const float p_n2 = knm * knm;
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 if (c ? hit1 : hit0) {
                     const float p_esc = rmx[c] * f_mx[c] + rmy[c] * f_my[c];
                     if (!(fabsf(p_esc - p_n2) > simil_t * p_n2)) {
-                        if (GREC) {
-                            const float n2m = f_mx[c] * f_mx[c] + f_my[c] * f_my[c];
-                            const float nm = sqrtf_mid(n2m);
-                            div2_mid_f32(f_mx[c], f_my[c], nm, f_ux[c], f_uy[c]);
-                        }
+                        if (GREC) grec_u_m(f_mx[c], f_my[c], f_ux[c], f_uy[c]);
                         const float dx = px[c] - f_cpx[c], dy = py[c] - f_cpy[c];
                         fi[c] = dx * f_ux[c] + dy * f_uy[c];
                         dfx[c] = f_ux[c];
@@ -1737,32 +1586,18 @@ __device__ __forceinline__ void tvr2_body_f32(const TvrArgs &a, const int seq, c
             }
         }
     }
-    unsigned long long below[2];
-    float inh[2];
+    WaveLast<float> wl[2];
 #pragma unroll
     for (int c = 0; c < 2; c++) {
-        const unsigned long long vmask = __ballot(status[c] == 2);
-        below[c] = vmask & ((1ull << lane) - 1ull);
-        const int src = below[c] ? 63 - __clzll(below[c]) : 0;
-        inh[c] = __shfl(fi[c], src, 64);
-        const int top = vmask ? 63 - __clzll(vmask) : 0;
-        const float wl = __shfl(fi[c], top, 64);
-        if (lane == 0) {
-            s_whas[c][wave] = vmask != 0;
-            s_wlast[c][wave] = wl;
-        }
+        wl[c] = wave_last_valid(fi[c], status[c] == 2, lane);
+        carry_publish(wl[c], lane, wave, s_wlast[c], s_whas[c]);
     }
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < 2; c++) {
         double *rout = c ? rout1 : rout0;
         if (status[c] == 3) {
-            double v = marker;
-            bool have = false;
-            if (below[c]) { v = (double)inh[c]; have = true; }
-            for (int pw = wave - 1; pw >= 0 && !have; pw--)
-                if (s_whas[c][pw]) { v = (double)s_wlast[c][pw]; have = true; }
-            rout[ikl] = v;
+            rout[ikl] = carry_inherit(wl[c], wave, s_wlast[c], s_whas[c]);
         } else if (status[c] == 2) {
             rout[ikl] = (double)fi[c];
         } else if (status[c] == 1) {
@@ -1773,12 +1608,8 @@ __device__ __forceinline__ void tvr2_body_f32(const TvrArgs &a, const int seq, c
     }
     if (tid == 0) {
 #pragma unroll
-        for (int c = 0; c < 2; c++) {
-            double bl = marker;
-            for (int pw = NW - 1; pw >= 0; pw--)
-                if (s_whas[c][pw]) { bl = (double)s_wlast[c][pw]; break; }
-            (c ? a.block_last : a.block_last_z)[(size_t)seq * a.nblk + blk] = bl;
-        }
+        for (int c = 0; c < 2; c++)
+            (c ? a.block_last : a.block_last_z)[(size_t)seq * a.nblk + blk] = carry_block_last(s_wlast[c], s_whas[c]);
     }
     __shared__ float s_red[2][NW][32];
     const double inv_q = 1.0 / s_rho;
@@ -1788,50 +1619,29 @@ __device__ __forceinline__ void tvr2_body_f32(const TvrArgs &a, const int seq, c
         float f = fm[c];
         if (ikl < kn) {
             if (PROCJF) {
-                float t0 = zf * rho_p[c];
-                J[0] = t0 * dfx[c];
-                J[1] = t0 * dfy[c];
-                t0 = rho_p[c] * pix[c];
-                J[2] = t0 * dfx[c];
-                t0 = rho_p[c] * piy[c];
-                J[2] += t0 * dfy[c];
-                J[3] = J[1] * ptz[c]; J[3] += J[2] * pty[c];
-                J[4] = J[0] * ptz[c]; J[4] += J[2] * ptx[c];
-                t0 = J[0] * pty[c];
-                J[5] = -1.f * t0; J[5] += J[1] * ptx[c];
+                jac_row(J, zf, rho_p[c], pix[c], piy[c], ptx[c], pty[c], ptz[c], dfx[c], dfy[c]);
 #pragma unroll
                 for (int j = 0; j < 6; j++) J[j] = (float)div_rn((double)J[j], s_rho, inv_q);
             }
             f = (float)div_rn((double)f, s_rho, inv_q);
         }
+        float sums[kNumSums];
+        int ns = 0;
         if (PROCJF) {
-            float sums[kNumSums];
-            int ns = 0;
 #pragma unroll
             for (int i = 0; i < 6; i++)
 #pragma unroll
                 for (int j = i; j < 6; j++) sums[ns++] = J[i] * J[j];
 #pragma unroll
             for (int i = 0; i < 6; i++) sums[ns++] = J[i] * f;
-            sums[ns] = f * f;
-            const int idx = wave_reduce28_f32(sums, lane);
-            if ((lane & 1) == 0) s_red[c][wave][idx] = sums[0];
-        } else {
-            float v = f * f;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if (lane == 0) s_red[c][wave][kNumSums - 1] = v;
         }
+        sums[PROCJF ? ns : kNumSums - 1] = f * f;
+        block_reduce_put<PROCJF>(sums, lane, wave, s_red[c]);
     }
     __syncthreads();
-    if (wave < 2) {
+    if (wave < 2) {   // wave 0 finishes chain 1, wave 1 chain 0
         const int c = 1 - wave;
-        if (PROCJF ? lane < kNumSums : lane == kNumSums - 1) {
-            float v = s_red[c][0][lane];
-#pragma unroll
-            for (int wv = 1; wv < NW; wv++) v += s_red[c][wv][lane];
-            (c ? a.partials : a.partials_z)[((size_t)seq * a.nblk + blk) * kNumSums + lane] = (double)v;
-        }
+        block_reduce_store<PROCJF>(s_red[c], lane, (c ? a.partials : a.partials_z) + ((size_t)seq * a.nblk + blk) * kNumSums);
     }
 }
 template <bool PROCJF, bool GREC>
@@ -1858,13 +1668,12 @@ __device__ __forceinline__ void tvr_rw2_body(const TvrArgs &a, const int seq, co
     SeqDev *sq = a.seq + seq;
     const int kn = a.kn_old[seq];
     if (blk * 2 * kTvrBlock >= kn) return;  // whole block beyond the list (block-uniform)
-    static_assert(kTvrPasses == 1 && kTvrThreads == kTvrBlock, "one KeyLine per thread and carry granule");
+    static_assert(kTvrThreads == kTvrBlock, "a half is one carry granule");
     const KlSoA &ko = a.kl_old[seq];
     const int res_in = sq->res_cur, res_out = sq->lm_phase == 0 ? sq->res_t : sq->res_new;
     const double *rin = a.resid + ((size_t)res_in * a.nseq + seq) * a.cap;
     double *rout = a.resid + ((size_t)res_out * a.nseq + seq) * a.cap;
     const double *carry_row = a.resid_carry + ((size_t)res_in * a.nseq + seq) * a.nblk;
-    const double marker = __longlong_as_double((long long)resid_carry_bits());
     constexpr int NW = kTvrThreads / 64;
     __shared__ double s_wlast[2][NW];
     __shared__ int s_whas[2][NW];
@@ -1945,15 +1754,8 @@ __device__ __forceinline__ void tvr_rw2_body(const TvrArgs &a, const int seq, co
     const bool hit0 = inimg[0] && f0 != 0u, hit1 = inimg[1] && f1 != 0u;
     const int ikf0 = hit0 ? (int)f0 - 1 : 0, ikf1 = hit1 ? (int)f1 - 1 : 0;
     float f_cpx[2], f_cpy[2], f_mx[2], f_my[2], f_ux[2] = {0, 0}, f_uy[2] = {0, 0};
-    if (GREC) {
-        const float4 g0 = ldg(a.kl_new[seq].grec, ikf0), g1 = ldg(a.kl_new[seq].grec, ikf1);
-        f_cpx[0] = g0.x; f_cpy[0] = g0.y; f_mx[0] = g0.z; f_my[0] = g0.w;
-        f_cpx[1] = g1.x; f_cpy[1] = g1.y; f_mx[1] = g1.z; f_my[1] = g1.w;
-    } else {
-        const MatchRec r0 = a.kl_new[seq].rec[ikf0], r1 = a.kl_new[seq].rec[ikf1];
-        f_cpx[0] = r0.c_px; f_cpy[0] = r0.c_py; f_mx[0] = r0.m_mx; f_my[0] = r0.m_my; f_ux[0] = r0.u_mx; f_uy[0] = r0.u_my;
-        f_cpx[1] = r1.c_px; f_cpy[1] = r1.c_py; f_mx[1] = r1.m_mx; f_my[1] = r1.m_my; f_ux[1] = r1.u_mx; f_uy[1] = r1.u_my;
-    }
+    load_matched<GREC>(a.kl_new[seq], ikf0, f_cpx[0], f_cpy[0], f_mx[0], f_my[0], f_ux[0], f_uy[0]);
+    load_matched<GREC>(a.kl_new[seq], ikf1, f_cpx[1], f_cpy[1], f_mx[1], f_my[1], f_ux[1], f_uy[1]);
 #pragma unroll
     for (int c = 0; c < 2; c++) {
         if (c ? hit1 : hit0) {
@@ -1976,31 +1778,17 @@ __device__ __forceinline__ void tvr_rw2_body(const TvrArgs &a, const int seq, co
         }
     }
     // ---- DResidualNew: each half is a block of its own for the "last valid fi" propagation (tvr_body's rule) ----
-    unsigned long long below[2];
-    double inh[2];
+    WaveLast<double> wl[2];
 #pragma unroll
     for (int c = 0; c < 2; c++) {
-        const unsigned long long vmask = __ballot(status[c] == 2);
-        below[c] = vmask & ((1ull << lane) - 1ull);
-        const int src = below[c] ? 63 - __clzll(below[c]) : 0;
-        inh[c] = __shfl(fi[c], src, 64);
-        const int top = vmask ? 63 - __clzll(vmask) : 0;
-        const double wl = __shfl(fi[c], top, 64);
-        if (lane == 0) {
-            s_whas[c][wave] = vmask != 0;
-            s_wlast[c][wave] = wl;
-        }
+        wl[c] = wave_last_valid(fi[c], status[c] == 2, lane);
+        carry_publish(wl[c], lane, wave, s_wlast[c], s_whas[c]);
     }
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < 2; c++) {
         if (status[c] == 3) {
-            double v = marker;
-            bool have = false;
-            if (below[c]) { v = inh[c]; have = true; }
-            for (int pw = wave - 1; pw >= 0 && !have; pw--)
-                if (s_whas[c][pw]) { v = s_wlast[c][pw]; have = true; }
-            rout[ikl[c]] = v;
+            rout[ikl[c]] = carry_inherit(wl[c], wave, s_wlast[c], s_whas[c]);
         } else if (status[c] == 2) {
             rout[ikl[c]] = fi[c];
         } else if (status[c] == 1) {
@@ -2017,10 +1805,7 @@ __device__ __forceinline__ void tvr_rw2_body(const TvrArgs &a, const int seq, co
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             if ((2 * blk + c) * kTvrBlock >= kn || 2 * blk + c >= a.nblk) continue;
-            double bl = marker;
-            for (int pw = NW - 1; pw >= 0; pw--)
-                if (s_whas[c][pw]) { bl = s_wlast[c][pw]; break; }
-            a.block_last[(size_t)seq * a.nblk + 2 * blk + c] = bl;
+            a.block_last[(size_t)seq * a.nblk + 2 * blk + c] = carry_block_last(s_wlast[c], s_whas[c]);
         }
     }
     // ---- Jacobian rows, weights, the 28 sums of both KeyLines, one reduction ----
@@ -2035,17 +1820,7 @@ __device__ __forceinline__ void tvr_rw2_body(const TvrArgs &a, const int seq, co
 #if EDGEHIP_TVR_REF_ORDER
             fmc *= inv_w2[c]; dfx[c] *= inv_w2[c]; dfy[c] *= inv_w2[c];
 #endif
-            double t0 = a.zfm * rho_p[c];
-            J[0] = t0 * dfx[c];
-            J[1] = t0 * dfy[c];
-            t0 = rho_p[c] * pix[c];
-            J[2] = t0 * dfx[c];
-            t0 = rho_p[c] * piy[c];
-            J[2] += t0 * dfy[c];
-            J[3] = J[1] * ptz[c]; J[3] += J[2] * pty[c];
-            J[4] = J[0] * ptz[c]; J[4] += J[2] * ptx[c];
-            t0 = J[0] * pty[c];
-            J[5] = -1 * t0; J[5] += J[1] * ptx[c];
+            jac_row(J, a.zfm, rho_p[c], pix[c], piy[c], ptx[c], pty[c], ptz[c], dfx[c], dfy[c]);
             const double qvel = (a.zfm * dfx[c] * V[0] + a.zfm * dfy[c] * V[1] + (pix[c] * dfx[c] + piy[c] * dfy[c]) * V[2]);
 #if EDGEHIP_TVR_REF_ORDER
             const double q_rho = sqrt(s_rho[c] * qvel * s_rho[c] * qvel + 1), r_q = 1.0 / q_rho;
@@ -2070,16 +1845,11 @@ __device__ __forceinline__ void tvr_rw2_body(const TvrArgs &a, const int seq, co
         sums[ns] += fmc * fmc;
     }
     __shared__ double s_red[NW][32];
-    const int idx = wave_reduce28(sums, lane);
-    if ((lane & 1) == 0) s_red[wave][idx] = sums[0];
+    double *prow = a.partials + ((size_t)seq * a.nblk + 2 * blk) * kNumSums;
+    block_reduce_put<true>(sums, lane, wave, s_red);
     __syncthreads();
-    if (tid < kNumSums) {
-        double v = s_red[0][tid];
-#pragma unroll
-        for (int wv = 1; wv < NW; wv++) v += s_red[wv][tid];
-        a.partials[((size_t)seq * a.nblk + 2 * blk) * kNumSums + tid] = v;
-        if (2 * blk + 1 < a.nblk) a.partials[((size_t)seq * a.nblk + 2 * blk + 1) * kNumSums + tid] = 0.0;   // the LM step adds one row per 256 KeyLines
-    }
+    block_reduce_store<true>(s_red, tid, prow);
+    if (tid < kNumSums && 2 * blk + 1 < a.nblk) prow[kNumSums + tid] = 0.0;   // the LM step adds one row per 256 KeyLines
 }
 
 template <bool GREC>
@@ -2550,6 +2320,9 @@ __device__ __forceinline__ void lm_body(const LmArgs &a, const int seq, const in
         if (prefetch) {
             // resolve the carries across the lanes: block b starts from the last valid residual of the blocks before it
             // (fi = 0 at the top): the newest valid lane below b, found in the ballot
+            // (wave_last_valid's lower half, resid_carry.h, written out: through the helper k_lm_step, k_lm_step2 and k_tvr_prepare_begin
+            // come out with one multiplication commuted, and B.tvr_prepare then measured 1.2 us slower against a parent spread of 0.8 us,
+            // profiles/tracker_carry_refactor.txt; as it stands the three kernels' instruction streams are the ones they had)
             const bool valid = lane < nblk_used && !is_carry(bl_pre);
             const unsigned long long vm = __ballot(valid);
             const unsigned long long below = vm & ((1ull << lane) - 1ull);
@@ -2828,7 +2601,6 @@ __global__ __launch_bounds__(256) void k_try_vel(TvrArgs a) {
     const int ikl = blk * 256 + tid;
     const KlSoA &ko = a.kl_old[seq];
     double *res = a.resid + (size_t)seq * a.cap;            // residual buffer 0, updated in place
-    const double marker = __longlong_as_double((long long)resid_carry_bits());
     const double *V = USE_NEW ? sq->mv_Vnew : sq->mv_V;
     const double v0 = V[0], v1 = V[1], v2 = V[2];
     double s[kTvNum];
@@ -2926,33 +2698,25 @@ __global__ __launch_bounds__(256) void k_try_vel(TvrArgs a) {
             }
         }
     }
-    // Residuals[ikl] = fabs(fi) with fi only refreshed by a match: "last valid" propagation as in k_try_velrot
+    // Residuals[ikl] = fabs(fi) with fi only refreshed by a match: the "last valid" propagation of resid_carry.h on |fi|
+    // (carry_publish and carry_block_last stay written out here: through the helpers this kernel gains a vector instruction; as it
+    // stands its instruction stream is the one it had before the helpers)
     __shared__ double s_wlast[4];
     __shared__ int s_whas[4];
     {
         const double afi = fabs(fi);
-        const unsigned long long vmask = __ballot(status == 2);
-        const unsigned long long below = vmask & ((1ull << lane) - 1ull);
-        const int src = below ? 63 - __clzll(below) : 0;
-        const double inh = __shfl(afi, src, 64);
-        const int top = vmask ? 63 - __clzll(vmask) : 0;
-        const double wl = __shfl(afi, top, 64);
-        if (lane == 0) { s_whas[wave] = vmask != 0; s_wlast[wave] = wl; }
+        const WaveLast<double> wl = wave_last_valid(afi, status == 2, lane);
+        if (lane == 0) { s_whas[wave] = wl.any; s_wlast[wave] = wl.top; }
         __syncthreads();
         if (status == 3) {
-            double v = marker;
-            bool have = false;
-            if (below) { v = inh; have = true; }
-            for (int pw = wave - 1; pw >= 0 && !have; pw--)
-                if (s_whas[pw]) { v = s_wlast[pw]; have = true; }
-            res[ikl] = v;
+            res[ikl] = carry_inherit(wl, wave, s_wlast, s_whas);
         } else if (status == 2) {
             res[ikl] = afi;
         } else if (ikl < kn) {
             res[ikl] = resolved ? rkeep : res_old;   // unchanged entries are rewritten too: whole-line stores (a partial line is a read-modify-write)
         }
         if (tid == 0) {
-            double bl = marker;
+            double bl = carry_marker();
             for (int pw = 3; pw >= 0; pw--)
                 if (s_whas[pw]) { bl = s_wlast[pw]; break; }
             a.block_last[(size_t)seq * a.nblk + blk] = bl;
@@ -3063,12 +2827,8 @@ __global__ __launch_bounds__(64) void k_lmv_step(SeqDev *seqs, const double *__r
         }
         // carries: |fi| of the last matched KeyLine before each block (0 at the top: double fi=0)
         if (pre) {
-            const bool valid = lane < nblk_used && !is_carry(bl);
-            const unsigned long long vm = __ballot(valid);
-            const unsigned long long below = vm & ((1ull << lane) - 1ull);
-            const int src = below ? 63 - __clzll(below) : 0;
-            const double inh = __shfl(bl, src, 64);
-            if (lane < nblk_used) carry[(size_t)seq * nblk + lane] = below ? inh : 0.0;
+            const WaveLast<double> wl = wave_last_valid(bl, lane < nblk_used && !is_carry(bl), lane);
+            if (lane < nblk_used) carry[(size_t)seq * nblk + lane] = wl.has_below ? wl.inh : 0.0;
         } else if (lane == 32) {
             double run = 0;
             for (int b = 0; b < nblk_used; b++) {

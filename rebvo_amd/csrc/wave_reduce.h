@@ -156,6 +156,43 @@ __device__ __forceinline__ int wave_reduce28_f32(float (&s)[kNumSums], int lane)
     return low == 7 ? 31 : low + 7 * b4 + 14 * b5;
 }
 
+__device__ __forceinline__ int wave_reduce28(float (&s)[kNumSums], int lane) { return wave_reduce28_f32(s, lane); }
+
+// ---------------------------------------------------------------------------------------------------
+// The block reduction that finishes an evaluation's 28 sums (T = double, or float for the float tracker; NW waves per block), in
+// three steps over the caller's s_red[NW][32]:
+//   block_reduce_put    every wave: the transposed reduction above and one row of s_red — or, for a score-only evaluation (!PROCJF:
+//                       f^T f alone, sums[kNumSums - 1]), the plain xor butterfly on that one value (block_reduce_put_score: a body
+//                       that never forms the other 27 sums hands the value over directly),
+//   a barrier           (one for both chains in a two-chain body),
+//   block_reduce_store  threads t = 0 .. 27 of one wave: the waves' rows added left to right, s_red[0] + s_red[1] + ... (fixed
+//                       order: deterministic), and stored to the block's row of `partials`, which is always a double.
+// ---------------------------------------------------------------------------------------------------
+template <typename T, int NW>
+__device__ __forceinline__ void block_reduce_put_score(T v, const int lane, const int wave, T (&s_red)[NW][32]) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane == 0) s_red[wave][kNumSums - 1] = v;
+}
+template <bool PROCJF, typename T, int NW>
+__device__ __forceinline__ void block_reduce_put(T (&sums)[kNumSums], const int lane, const int wave, T (&s_red)[NW][32]) {
+    if (PROCJF) {
+        const int idx = wave_reduce28(sums, lane);
+        if ((lane & 1) == 0) s_red[wave][idx] = sums[0];
+    } else {
+        block_reduce_put_score(sums[kNumSums - 1], lane, wave, s_red);
+    }
+}
+template <bool PROCJF, typename T, int NW>
+__device__ __forceinline__ void block_reduce_store(const T (&s_red)[NW][32], const int t, double *partials_row) {
+    if (PROCJF ? t < kNumSums : t == kNumSums - 1) {
+        T v = s_red[0][t];
+#pragma unroll
+        for (int wv = 1; wv < NW; wv++) v += s_red[wv][t];
+        partials_row[t] = (double)v;
+    }
+}
+
 // The same for up to 16 values (the 3-DoF tracker's 10): 16 -> 8 -> 4 -> 2 -> 1 over lane ^ 32, 16, 8, 4, then the two
 // remaining butterfly steps (lane ^ 2, lane ^ 1) on the single value.  On return v[0] of lane l is the full sum of value
 //     idx = 8*b5 + 4*b4 + 2*b3 + b2      (b_k = bit k of l), the same in all four lanes of a quad.
