@@ -1027,6 +1027,72 @@ int edgehip_keyframe_depth_select(edgehip_ctx *ctx, const uint8_t *mask);
 /* Device time of the last of the three calls above, by HIP events (waits for that call's end). */
 int edgehip_keyframe_depth_ms(edgehip_ctx *ctx, double *ms);
 
+/* ---- the frame as a baseline JPEG (the MJPEG video path) --------------------------------------------------------------------
+ * What the reference's output thread does with a finished frame before it sends or saves it (rebvo_third_t.cpp:184-257): MJPEGEncoder
+ * at quality 90 (video_mjpeg.cpp:63-74), i.e. gdImageJpegPtr, i.e. libjpeg after jpeg_set_defaults and jpeg_set_quality(q, TRUE):
+ * baseline, 8 bit, YCbCr 4:2:0, the Annex-K Huffman tables (not optimised), the islow integer DCT, no restart markers.  The device
+ * encoder follows that in integers only (the rule is written out in rebvo/jpeg_encode.h and DESIGN.md §19) and its stream is libjpeg's
+ * byte for byte: SOI, APP0 (JFIF 1.01, units 0, density 1x1, no thumbnail), the optional COM segment, DQT 0, DQT 1, SOF0, four DHT, SOS
+ * (623 bytes without a comment), the entropy-coded data, EOI.  An image's bytes do not depend on the batch it is encoded in.
+ * What could NOT be compared is gd's own decoration of the header, because no libgd was available where this was written: gd writes a
+ * COM segment of the form "CREATOR: gd-jpeg v1.0 (using IJG JPEG v<N>), quality = 90\n" (pass that text as `comment` to get it at the
+ * place jpeg_write_marker puts it, directly behind APP0), and newer gd versions write the image's resolution into APP0's density
+ * fields, which stay 1x1 without units here. */
+typedef struct edgehip_jpeg_size {
+    uint32_t size;          /* the stream's true length in bytes, also when it did not fit */
+    uint32_t overflow;      /* 1: size > cap_bytes; the region then holds the stream's first cap_bytes bytes */
+} edgehip_jpeg_size;
+/* No stream of a w x h image is longer than this: 623 + the COM segment (comment_len + 4, when there is one) + 2 * ceil(nblocks *
+ * (22 + 63 * 26) / 8) + 2 with nblocks = 6 * ceil(w / 16) * ceil(h / 16) — every block at its longest code, every data byte stuffed.
+ * 0 for w or h < 1. */
+uint64_t edgehip_jpeg_bound(int w, int h, uint32_t comment_len);
+/* Allocates the store: nseq regions of cap_bytes (each starting on a 16-byte boundary: the stride is cap_bytes rounded up to 16), nseq
+ * size records, the tables of `quality` and the header (with `comment`, a C string, as COM segment; NULL: none), all regions zero.
+ * cap_bytes == 0 frees the store.  EDGEHIP_ERR_ARG for a quality outside 1..100, a comment above 65533 bytes or a cap_bytes below
+ * header + EOI; EDGEHIP_ERR_MEMORY when the allocation fails (the store is then off; the context stays usable). */
+int edgehip_jpeg_enable(edgehip_ctx *ctx, int quality, uint32_t cap_bytes, const char *comment /* or NULL */);
+/* The frame every sequence holds in `slot` becomes one JPEG in the sequence's region, in-stream (no synchronisation).  The frame is
+ * read where stage A reads it — the slot's RGB24 or 8-bit mono storage (a mono value v is R = G = B = v: Y = v, Cb = Cr = 128), or the
+ * frames of a bound pool — and, on a context with use_undistort, resampled as edgehip_download_undistorted resamples it (what
+ * PipeBuffer::imgc holds).  A stream longer than cap_bytes leaves its true size and the overflow flag in the record and its first
+ * cap_bytes bytes in the region; nothing is written past a region.  Uploads enqueued afterwards (into any slot: the upload streams
+ * wait as a whole) wait for the encoder's reads, so call it where the next frame's upload may wait for the frame before.
+ * edgehip_process_frame enqueues nothing of this.  A slot that never received a frame is encoded as its storage stands (zeros after
+ * edgehip_create).  EDGEHIP_ERR_STATE when the store is off, EDGEHIP_ERR_ARG for a slot out of range. */
+int edgehip_jpeg_encode(edgehip_ctx *ctx, int slot);
+/* Restricts edgehip_jpeg_encode to the sequences with mask[seq] != 0 (mask[nseq]; NULL: every sequence again, the default): the regions
+ * and size records of the others stay as they are.  Holds until changed or until the store is freed.  Synchronises (mask != NULL). */
+int edgehip_jpeg_select(edgehip_ctx *ctx, const uint8_t *mask);
+/* Sequence seq's stream: min(size, cap_bytes, cap) bytes into dst (may be NULL), the record into *size (may be NULL).  Synchronises. */
+int edgehip_download_jpeg(edgehip_ctx *ctx, int seq, uint8_t *dst, uint32_t cap, edgehip_jpeg_size *size);
+/* The same for n sequences seqs[n] (dst[j] with room for cap bytes each, sizes[n]; either array or any dst[j] may be NULL): the
+ * records in one copy, then the streams.  Synchronises twice at most, whatever n. */
+int edgehip_download_jpeg_batch(edgehip_ctx *ctx, int n, const int32_t *seqs, uint8_t *const *dst, uint32_t cap, edgehip_jpeg_size *sizes);
+/* The regions of sequences [first, first + count) into DEVICE memory of the context's GPU: bytes_dev[count][stride] with stride =
+ * cap_bytes rounded up to 16, sizes_dev[count] records (either may be NULL; e.g. torch uint8 tensors), without a host bounce — like
+ * edgehip_net_keylines_device.  The copy is complete on return. */
+int edgehip_jpeg_device(edgehip_ctx *ctx, int first, int count, void *bytes_dev, void *sizes_dev);
+/* For output callbacks at full pipeline depth, through a staging ring like edgehip_export_keylines' (four tickets): the frames that
+ * sequences seqs[n] hold in `slot` are encoded in-stream (no synchronisation) into a ring entry, n regions in the order of seqs; the
+ * slot's frames and the store's regions are free again as far as the export goes.  edgehip_jpeg_export_sizes(ticket, sizes[n]) waits
+ * for that encoder alone (an event, no stream) and gives the records; edgehip_jpeg_export_fetch(ticket, dst[n]) enqueues the copies
+ * of min(size, cap_bytes) bytes each on the ring's own stream (dst[j] NULL: skipped; straight into memory of edgehip_register_host,
+ * through a page-locked mirror otherwise) and does not wait for them; edgehip_jpeg_export_wait(ticket) blocks until they have landed
+ * (a ticket never fetched: until its encoder has run) and releases the ticket.  The select mask does not apply.  EDGEHIP_ERR_STATE
+ * when the store is off or four tickets are outstanding; edgehip_jpeg_enable drops outstanding tickets. */
+int edgehip_jpeg_export(edgehip_ctx *ctx, int slot, int n, const int32_t *seqs, int *ticket_out);
+int edgehip_jpeg_export_sizes(edgehip_ctx *ctx, int ticket, edgehip_jpeg_size *sizes);
+int edgehip_jpeg_export_fetch(edgehip_ctx *ctx, int ticket, uint8_t *const *dst);
+int edgehip_jpeg_export_wait(edgehip_ctx *ctx, int ticket);
+/* The stage-level, geometry-free entry: `count` packed RGB24 images of w x h >= 1 x 1 in device memory (image i at rgb24_dev + i * w *
+ * h * 3) through the same kernel, image i's stream to out_dev + i * cap and its record to sizes_dev[i] (edgehip_jpeg_size).  The
+ * context's own sizes are multiples of 8 or 16 and never reach the padding and dummy-block rules; this entry does (tests), and it
+ * compresses what is already on the device, e.g. edgehip_depth_image renderings.  No comment segment.  cap is a multiple of 16 and at
+ * least 625, out_dev 16-byte aligned, w and h at most 65535 with w * h * 3 < 2^31 and edgehip_jpeg_bound(w, h, 0) < 2^31 (sizes and caps
+ * are 32-bit: about 320 megapixels; EDGEHIP_ERR_ARG beyond, as in edgehip_jpeg_enable); needs no store.  The images are done on return. */
+int edgehip_jpeg_encode_images(edgehip_ctx *ctx, const void *rgb24_dev, int w, int h, int count, int quality, void *out_dev, uint32_t cap,
+                               void *sizes_dev);
+
 /* ---- measurement ------------------------------------------------------------------------------------- */
 /* Names of the kernel groups timed by the built-in HIP-event profiler, and their accumulated device time.
  * edgehip_profile_enable(ctx, 1) brackets every launch group with events on the context stream (adds host

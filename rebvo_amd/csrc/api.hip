@@ -650,6 +650,7 @@ int edgehip_destroy(edgehip_ctx *c) {
     net_free(c);
     ros_free(c);
     kf_track_free(c);
+    jpeg_free(c);
     CtxAllocs *mine = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_allocs_mu);
@@ -673,6 +674,7 @@ int edgehip_destroy(edgehip_ctx *c) {
     if (c->aos_dev) { (void)hipFree(c->aos_dev); (void)hipHostFree(c->aos_host); (void)hipFree(c->aos_req_dev); (void)hipHostFree(c->aos_req_host); }
     c->kl_ring.close();
     c->ros_ring.close();
+    c->jpeg_ring.close();
     if (c->stream_log) {
         (void)hipStreamSynchronize(c->stream_log); (void)hipStreamDestroy(c->stream_log); (void)hipEventDestroy(c->ev_log);
         for (hipEvent_t e : c->ev_log_ring) if (e) (void)hipEventDestroy(e);

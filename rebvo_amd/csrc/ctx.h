@@ -522,6 +522,7 @@ struct edgehip_ctx {
     int aos_requests = 0;
     // The lists of output callbacks without a host synchronisation, one staging ring (export_ring.h) per product:
     edgehip::ExportRing kl_ring;    // edgehip_export_keylines / _fetch / _wait: [n_cap][CAP] AoS KeyLine records per entry, int32 sequence ids per row
+    edgehip::ExportRing jpeg_ring;  // edgehip_jpeg_export / _sizes / _fetch / _wait: [n_cap] regions | size records per entry, sequence ids | size records per row (jpeg_encode.hip)
     edgehip::ExportRing ros_ring;   // edgehip_ros_export / _fetch / _wait: points | records per entry, k_prof | sequence ids per row (ros_edgemap.hip)
     edgehip_nav *nav_dev;  // [B] per-frame record
     edgehip_nav *nav_log;  // [nav_log_len][B] ring of per-frame records (optional)
@@ -585,6 +586,9 @@ struct edgehip_ctx {
     // edgehip_keyframe_track_enable: every sequence's current key frame and the scratch of the match repair (keyframe_track.hip); null when off
     struct KfTrack;
     KfTrack *kftrack = nullptr;
+    // edgehip_jpeg_enable: every sequence's frame as a baseline JPEG, its size records, tables and header (jpeg_encode.hip); null when off
+    struct JpegStore;
+    JpegStore *jpeg = nullptr;
 };
 
 namespace edgehip {
@@ -707,6 +711,7 @@ void net_free(edgehip_ctx *c);                      // net_keyline.hip: edgehip_
 bool net_store(edgehip_ctx *c, const uint8_t **records, const edgehip_net_header **headers, int *kl_size);
 void surface_views_free(edgehip_ctx *c);            // surface_integrate.hip
 void ros_free(edgehip_ctx *c);                      // ros_edgemap.hip: the stores, edgehip_destroy
+void jpeg_free(edgehip_ctx *c);                     // jpeg_encode.hip: edgehip_jpeg_enable(ctx, q, 0, NULL), edgehip_destroy
 void kf_track_free(edgehip_ctx *c);                 // keyframe_track.hip: edgehip_keyframe_track_enable(ctx, 0, ...), edgehip_destroy
 int kf_track_reset_enqueue(edgehip_ctx *c);         // edgehip_reset: no key frame, empty records (no-op when off)
 // keyframe_track.hip, the frame driver's hooks (only with c->kftrack): the first-key-frame rule on the old slot at the frame's begin

@@ -321,6 +321,9 @@ EXPORTS = [
     "edgehip_keyframe_constraint", "edgehip_keyframe_mutual_exclusion", "edgehip_keyframe_constraint_ms",
     "edgehip_keyframe_map_depth", "edgehip_keyframe_translate_depth", "edgehip_keyframe_list_translate_depth", "edgehip_keyframe_depth_ms",
     "edgehip_keyframe_depth_select",
+    "edgehip_jpeg_bound", "edgehip_jpeg_enable", "edgehip_jpeg_encode", "edgehip_jpeg_select", "edgehip_download_jpeg",
+    "edgehip_download_jpeg_batch", "edgehip_jpeg_device", "edgehip_jpeg_encode_images",
+    "edgehip_jpeg_export", "edgehip_jpeg_export_sizes", "edgehip_jpeg_export_fetch", "edgehip_jpeg_export_wait",
 ]
 
 _lib = None
@@ -337,6 +340,7 @@ def load_library():
         _lib.edgehip_last_error.restype = C.c_char_p
         _lib.edgehip_profile_name.restype = C.c_char_p
         _lib.edgehip_stream.restype = C.c_void_p
+        _lib.edgehip_jpeg_bound.restype = C.c_uint64
     return _lib
 
 
@@ -354,6 +358,11 @@ def build_undistort_map(params):
     if rc != 0:
         raise EdgeHipError(f"edgehip_build_undistort_map: {rc}")
     return inx, iw
+
+
+def jpeg_bound(w, h, comment_len=0):
+    """edgehip_jpeg_bound: no JPEG stream of a w x h frame is longer (host only)."""
+    return int(load_library().edgehip_jpeg_bound(int(w), int(h), C.c_uint32(int(comment_len))))
 
 
 def _dp(a):
@@ -432,6 +441,8 @@ class EdgeHip:
         self.p, self.nseq, self.nslots = params, nseq, nslots
         self.w, self.h, self.cap = params.w, params.h, min(params.max_points, 50000)
         self.ros_what = 0   # the stores edgehip_ros_enable has switched on through this wrapper
+        self.device = device
+        self.jpeg_cap = 0   # edgehip_jpeg_enable's cap_bytes
         self.ctx = C.c_void_p()
         self._ck(self.lib.edgehip_create(C.byref(params), nseq, nslots, device, C.byref(self.ctx)))
 
@@ -1383,6 +1394,95 @@ class EdgeHip:
         ms = C.c_double(0)
         self._ck(self.lib.edgehip_keyframe_depth_ms(self.ctx, C.byref(ms)))
         return ms.value
+
+    # ---- the frame as a baseline JPEG (libjpeg's stream at the settings gd leaves it with) ----
+    def jpeg_enable(self, quality=90, cap_bytes=None, comment=None):
+        """edgehip_jpeg_enable: one region of cap_bytes per sequence (None: edgehip_jpeg_bound of the context's frame, which no stream
+        exceeds; 0 frees the store), the tables of `quality`, `comment` (bytes or str) as COM segment."""
+        if isinstance(comment, str):
+            comment = comment.encode()
+        if cap_bytes is None:
+            cap_bytes = jpeg_bound(self.w, self.h, len(comment or b""))
+        self._ck(self.lib.edgehip_jpeg_enable(self.ctx, int(quality), C.c_uint32(int(cap_bytes)), comment))
+        self.jpeg_cap = int(cap_bytes)
+
+    def jpeg_encode(self, slot):
+        """edgehip_jpeg_encode: every (selected) sequence's frame of `slot` into its region (in-stream)."""
+        self._ck(self.lib.edgehip_jpeg_encode(self.ctx, int(slot)))
+
+    def jpeg_select(self, mask=None):
+        """Restrict jpeg_encode to the sequences with mask[seq] true (None: every sequence again)."""
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(bool), np.uint8)
+        assert m is None or m.shape == (self.nseq,)
+        self._ck(self.lib.edgehip_jpeg_select(self.ctx, None if m is None else m.ctypes.data_as(C.c_void_p)))
+
+    def jpeg_download(self, seq, with_record=False):
+        """edgehip_download_jpeg -> the stream as a uint8 array (its first cap_bytes bytes when it overflowed); with_record: (stream,
+        true size, overflow flag)."""
+        return self.jpeg_download_batch([seq], with_record)[0]
+
+    def jpeg_download_batch(self, seqs, with_record=False):
+        """edgehip_download_jpeg_batch -> the streams in the order of seqs."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.int32)
+        n = len(seqs)
+        bufs = [np.zeros(self.jpeg_cap, np.uint8) for _ in range(n)]
+        rec = np.zeros((n, 2), np.uint32)
+        pd = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        self._ck(self.lib.edgehip_download_jpeg_batch(self.ctx, n, seqs.ctypes.data_as(C.c_void_p), pd, C.c_uint32(self.jpeg_cap),
+                                                      rec.ctypes.data_as(C.c_void_p)))
+        out = [b[:min(int(r[0]), self.jpeg_cap)].copy() for b, r in zip(bufs, rec)]
+        return [(o, int(r[0]), bool(r[1])) for o, r in zip(out, rec)] if with_record else out
+
+    def jpeg_export(self, slot, seqs):
+        """edgehip_jpeg_export: the frames of `seqs` in `slot` encoded in-stream into a ring entry -> ticket."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.int32)
+        t = C.c_int(0)
+        self._ck(self.lib.edgehip_jpeg_export(self.ctx, int(slot), len(seqs), seqs.ctypes.data_as(C.c_void_p), C.byref(t)))
+        return (t.value, len(seqs))
+
+    def jpeg_export_fetch(self, ticket):
+        """edgehip_jpeg_export_sizes + _fetch: waits for the ticket's encoder only, enqueues the copies (does not wait for them) ->
+        (streams, records (n, 2) uint32); the streams are valid after jpeg_export_wait."""
+        tk, n = ticket
+        rec = np.zeros((n, 2), np.uint32)
+        self._ck(self.lib.edgehip_jpeg_export_sizes(self.ctx, tk, rec.ctypes.data_as(C.c_void_p)))
+        bufs = [np.zeros(min(int(r[0]), self.jpeg_cap), np.uint8) for r in rec]
+        pd = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        self._ck(self.lib.edgehip_jpeg_export_fetch(self.ctx, tk, pd))
+        return bufs, rec
+
+    def jpeg_export_wait(self, ticket):
+        self._ck(self.lib.edgehip_jpeg_export_wait(self.ctx, ticket[0]))
+
+    def jpeg_device(self, bytes_out=None, sizes_out=None, first=0):
+        """edgehip_jpeg_device: the regions of sequences [first, first + count) into torch tensors on the context's device, bytes_out
+        uint8 (count, stride) with stride = cap_bytes rounded up to 16, sizes_out int32 / uint32 (count, 2) (either may be None)."""
+        t = bytes_out if bytes_out is not None else sizes_out
+        count = t.shape[0]
+        if bytes_out is not None:
+            assert bytes_out.dtype.itemsize == 1 and bytes_out.is_contiguous() and tuple(bytes_out.shape) == (count, (self.jpeg_cap + 15) & ~15)
+        if sizes_out is not None:
+            assert sizes_out.dtype.itemsize == 4 and sizes_out.is_contiguous() and tuple(sizes_out.shape) == (count, 2)
+        self._ck(self.lib.edgehip_jpeg_device(self.ctx, int(first), int(count),
+                                              C.c_void_p(bytes_out.data_ptr() if bytes_out is not None else None),
+                                              C.c_void_p(sizes_out.data_ptr() if sizes_out is not None else None)))
+
+    def jpeg_encode_images(self, images, quality=90, cap=None):
+        """edgehip_jpeg_encode_images: `images` (count, h, w, 3) uint8 — a numpy array, or a torch tensor on the context's device —
+        through the encoder's kernel -> [(stream, true size, overflow flag)].  cap: bytes per image (a multiple of 16; None: the bound)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        t = images if isinstance(images, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images, np.uint8)).to(dev)
+        assert t.dtype == torch.uint8 and t.dim() == 4 and t.shape[3] == 3 and t.is_contiguous() and t.device == dev
+        count, h, w = int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
+        cap = (jpeg_bound(w, h) + 15) & ~15 if cap is None else int(cap)
+        out = torch.zeros((count, cap), dtype=torch.uint8, device=dev)
+        rec = torch.zeros((count, 2), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)   # the tensors were made on torch's stream, the encoder runs on the context's
+        self._ck(self.lib.edgehip_jpeg_encode_images(self.ctx, C.c_void_p(t.data_ptr()), w, h, count, int(quality), C.c_void_p(out.data_ptr()),
+                                                     C.c_uint32(cap), C.c_void_p(rec.data_ptr())))
+        out, rec = out.cpu().numpy(), rec.cpu().numpy()
+        return [(o[:min(int(r[0]), cap)].copy(), int(r[0]), bool(r[1])) for o, r in zip(out, rec)]
 
     def download_plane(self, seq, which):
         idx = {"img0": 0, "img1": 1, "dog": 2, "dx": 3, "dy": 4}[which]

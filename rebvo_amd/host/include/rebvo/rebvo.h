@@ -414,6 +414,12 @@ struct PipeBuffer {
     const PointCloud *point_cloud = nullptr;       // (mirror only) &EdgeMapOutput PointCloud = 1: from exactly this buffer's edge map and K, valid
                                                    // during the output callback; null when off or the delivery carries no edge map
     const EdgeMapMsg *edge_map_msg = nullptr;      // (mirror only) &EdgeMapOutput KeylineMsg = 1: likewise
+    const uint8_t *jpeg = nullptr;                 // (mirror only) VideoSave or VideoNetEnabled, objects on the group engine: this frame as the
+    size_t jpeg_size = 0;                          // encoder hands it on (EncoderType 1: the JPEG, 0: the raw RGB24), valid during the output callback.
+                                                   // With UseUndistort the JPEG is of the undistorted frame (the reference's imgc); the raw
+                                                   // bytes of EncoderType 0 are the frame as the camera delivered it
+    const std::vector<unsigned char> *net_packet = nullptr;   // (mirror only) VideoNetEnabled: net_packet_hdr + this delivery's records (EdgeMapDelay
+                                                   // frames late) + that frame, what the third thread would send (rebvo/net_keypoint.h); same lifetime
 };
 
 namespace customCam {
@@ -462,6 +468,12 @@ class REBVO {
     std::map<const PipeBuffer *, std::unique_ptr<DepthImage>> df_images;
     std::map<const PipeBuffer *, std::unique_ptr<PointCloud>> em_clouds;   // &EdgeMapOutput: the products behind each ring buffer's pointers
     std::map<const PipeBuffer *, std::unique_ptr<EdgeMapMsg>> em_msgs;
+    std::map<const PipeBuffer *, std::vector<uint8_t>> video_frames;   // VideoSave / VideoNetEnabled: the encoded frame behind each ring buffer's jpeg
+    std::vector<char> video_save;   // VideoSave: VideoSaveBuffersize bytes, video_save_at of them filled; written to VideoSaveFile when the object stops
+    size_t video_save_at = 0;
+    bool wantsVideo() const { return params.VideoSave != 0 || params.VideoNetEnabled; }
+    std::map<const PipeBuffer *, std::vector<unsigned char>> net_packets;   // ... and the packet behind each ring buffer's net_packet
+    std::shared_ptr<class NetPacketRing> net_ring;   // VideoNetEnabled: the EdgeMapDelay + 1 packets in the making (rebvo/net_keypoint.h)
     BatchGroup *group = nullptr;
     int group_seat = -1;
     bool keyframeDepthRequest(void *req);   // keyframeMapDepth / keyframeTranslateDepth: a BatchGroup::DepthReq through the group's queue

@@ -40,6 +40,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <map>
 #include <atomic>
@@ -49,6 +50,7 @@
 
 #include "edgehip.h"
 #include "rebvo/datasetcam.h"
+#include "rebvo/net_keypoint.h"
 #include "rebvo/rebvo.h"
 #include "rebvo_internal.h"
 
@@ -193,6 +195,21 @@ public:
     bool thread_done = false;
     void serveCovis();
     void refuseCovis();
+    // VideoSave / VideoNetEnabled members: every step's frames as the third thread's encoder would hand them on (MJPEGEncoder at quality 90:
+    // edgehip_jpeg_export, or the raw frame), through the context's third staging ring.  The encoder runs in-stream ahead of the step
+    // (videoExport, launch()); when the step's records have been read its streams' lengths are known and the copies go out on the ring's
+    // stream, straight into the storage behind the frame's PipeBuffer (videoFetch, complete() of that step); they are waited for when the
+    // frame is handed over, one completion later, and appended to the VideoSave buffer in frame order (videoFinish).  Nothing here waits
+    // for a frame stream.
+    struct VideoExport { long step = -1; int ticket = 0; std::vector<int32_t> seats; std::vector<PipeBuffer *> buf; bool fetched = false; };
+    VideoExport vx_of[4];          // [step & 3]
+    bool jpeg_on = false;
+    uint32_t jpeg_cap = 0;
+    int videoExport(long step);
+    int videoFetch(long step, const std::vector<PipeBuffer *> &mine);
+    int videoFinish(VideoExport &vx);
+    void videoFlush();             // everything still out, oldest first (a member leaves, the thread ends)
+    static void videoAppend(REBVO *cf, const uint8_t *p, size_t bytes);
     int cb_depth = 2;              // steps in flight when somebody has a callback (REBVO_GROUP_CB_DEPTH=1: the round-5 behaviour, A/B)
 
     void threadMain();
@@ -475,6 +492,12 @@ void REBVO::groupDetach() {
     }
     if (st.out_thread.joinable()) st.out_thread.join();
     for (Image<RGB24Pixel> *&im : st.side_img) { delete im; im = nullptr; }
+    if (params.VideoSave && !params.VideoSaveFile.empty()) {   // rebvo_third_t.cpp:351-366: the buffer goes to the file when the object stops
+        std::ofstream video_of(params.VideoSaveFile, std::ios::out | std::ios::trunc | std::ios::binary);
+        if (video_of.is_open()) video_of.write(video_save.data(), (std::streamsize)video_save_at);
+        else std::cout << "\nREBVO: cannot open the video file " << params.VideoSaveFile << "\n";
+        video_save_at = 0;
+    }
     {
         std::unique_lock<std::mutex> reg(BatchGroup::regMutex());
         std::unique_lock<std::mutex> lk(g->mut);
@@ -540,6 +563,7 @@ void REBVO::BatchGroup::pinKeyLines(Seat &st, bool pin) {
 void REBVO::BatchGroup::closeSeat(Seat &st) {
     // shutdown of one member: the frame still held for it is not delivered (as in the reference); pass the quit flag on
     REBVO *cf = st.cf;
+    videoFlush();   // (every step has completed: what is out is fetched; the VideoSave buffer gets its last frames)
     if (st.kl_pinned) pinKeyLines(st, false);
     if (kf_track && !failed && st.frames > 0 && kfDrain((int)(&st - seats.data()), true) != 0)   // what is left of its list, and its current key frame
         std::cout << "REBVO(hip): key-frame list: " << edgehip_last_error() << "\n";
@@ -893,6 +917,8 @@ int REBVO::BatchGroup::launch(long step, const std::vector<double> &ts) {
             kf_save = save;
         }
     }
+    rc = videoExport(step);   // (in-stream, ahead of the frame: the encoder needs the frame's pixels only)
+    if (rc != 0) return rc;
     rc = edgehip_process_frame(hip, ts.data());
     if (rc != 0) return rc;
     const double tp1 = detail::now_s();
@@ -910,6 +936,14 @@ int REBVO::BatchGroup::launch(long step, const std::vector<double> &ts) {
         nb.dtp1 = tp0;   // start of the step; complete() turns it into the step's duration
         if (imu_mode) nb.imu = st.imu_data;
         nb.imgc_valid = false;
+        if (cf->wantsVideo()) {
+            std::vector<uint8_t> &v = cf->video_frames[&nb];
+            v.clear();   // (EncoderType 1: filled by videoFetch when this step completes)
+            if (cf->params.encoder_type == 0) {   // VideoEncoder: the frame itself, as the camera delivered it (no undistortion: see rebvo.h)
+                v.assign((const uint8_t *)st.cbuf->img->Data(), (const uint8_t *)st.cbuf->img->Data() + frame_bytes);
+                videoAppend(cf, v.data(), v.size());
+            }
+        }
         const bool listened = cf->haveCallBack() || cf->saveImg;
         if (st.out_inline && listened) {   // somebody listens now: from here on this member has its output thread
             st.out_inline = false;
@@ -987,6 +1021,83 @@ int REBVO::BatchGroup::launch(long step, const std::vector<double> &ts) {
     tm.buffers += detail::now_s() - tp1;
     tm.steps++;
     return 0;
+}
+
+// VideoSave: PopFrame into what is left of the buffer (video_mjpeg.cpp:55; rebvo_third_t.cpp:249-256)
+void REBVO::BatchGroup::videoAppend(REBVO *cf, const uint8_t *p, size_t bytes) {
+    if (!cf->params.VideoSave) return;
+    if (cf->video_save.empty() && cf->params.VideoSaveBuffersize > 0) cf->video_save.resize((size_t)cf->params.VideoSaveBuffersize);
+    const size_t n = std::min(bytes, cf->video_save.size() - cf->video_save_at);
+    if (n) std::memcpy(cf->video_save.data() + cf->video_save_at, p, n);
+    cf->video_save_at += n;
+}
+
+int REBVO::BatchGroup::videoExport(long step) {
+    VideoExport &vx = vx_of[step & 3];
+    vx.step = -1;
+    vx.seats.clear();
+    for (int i = 0; i < cap; i++) {
+        const Seat &st = seats[i];
+        if (st.running && st.cbuf && st.cf->wantsVideo() && st.cf->params.encoder_type == 1) vx.seats.push_back(i);
+    }
+    if (vx.seats.empty()) return 0;
+    if (!jpeg_on) {   // a region per member and ring entry; a stream longer than the raw frame is cut there (and reported)
+        jpeg_cap = (uint32_t)std::min<uint64_t>(edgehip_jpeg_bound(hp.w, hp.h, 0), frame_bytes);
+        const int rc = edgehip_jpeg_enable(hip, 90, jpeg_cap, nullptr);   // MJPEGEncoder(ImageSize, 90), rebvo_third_t.cpp:122
+        if (rc != 0) return rc;
+        jpeg_on = true;
+    }
+    const int rc = edgehip_jpeg_export(hip, edgehip_next_slot(hip), (int)vx.seats.size(), vx.seats.data(), &vx.ticket);
+    if (rc != 0) return rc;
+    vx.step = step;
+    vx.fetched = false;
+    vx.buf.assign(vx.seats.size(), nullptr);
+    return 0;
+}
+
+int REBVO::BatchGroup::videoFetch(long step, const std::vector<PipeBuffer *> &mine) {
+    VideoExport &vx = vx_of[step & 3];
+    if (vx.step != step || vx.fetched) return 0;
+    std::vector<edgehip_jpeg_size> sz(vx.seats.size());
+    int rc = edgehip_jpeg_export_sizes(hip, vx.ticket, sz.data());   // (the step's records have been read: its encoder ran before it)
+    if (rc != 0) return rc;
+    std::vector<uint8_t *> dst(vx.seats.size(), nullptr);
+    for (size_t j = 0; j < vx.seats.size(); j++) {
+        PipeBuffer *b = mine[vx.seats[j]];
+        if (!b) continue;   // (the member left)
+        if (sz[j].overflow) std::cout << "\nREBVO: a frame's JPEG is longer than the frame (" << sz[j].size << " bytes): cut\n";
+        std::vector<uint8_t> &v = seats[vx.seats[j]].cf->video_frames[b];
+        v.resize(std::min(sz[j].size, jpeg_cap));
+        vx.buf[j] = b;
+        dst[j] = v.data();
+    }
+    rc = edgehip_jpeg_export_fetch(hip, vx.ticket, dst.data());
+    vx.fetched = rc == 0;
+    return rc;
+}
+
+int REBVO::BatchGroup::videoFinish(VideoExport &vx) {
+    if (vx.step < 0) return 0;
+    vx.step = -1;
+    const int rc = edgehip_jpeg_export_wait(hip, vx.ticket);
+    if (rc != 0 || !vx.fetched) return rc;
+    for (size_t j = 0; j < vx.seats.size(); j++) {
+        if (!vx.buf[j]) continue;
+        REBVO *cf = seats[vx.seats[j]].cf;
+        const std::vector<uint8_t> &v = cf->video_frames[vx.buf[j]];
+        videoAppend(cf, v.data(), v.size());
+    }
+    return 0;
+}
+
+void REBVO::BatchGroup::videoFlush() {
+    for (int k = 0; k < 4; k++) {
+        VideoExport *oldest = nullptr;
+        for (VideoExport &vx : vx_of)
+            if (vx.step >= 0 && (!oldest || vx.step < oldest->step)) oldest = &vx;
+        if (!oldest) return;
+        if (videoFinish(*oldest) != 0) std::cout << "\nREBVO: JPEG export failed: " << edgehip_last_error() << "\n";
+    }
 }
 
 // edgehip_depth_fill on `slot` for all sequences (and edgehip_depth_surface), then the grids of sequences seq[j] into dst[j] and their
@@ -1072,6 +1183,7 @@ int REBVO::BatchGroup::rosFetch(Export &ex, const std::vector<PipeBuffer *> &buf
 
 // Every export still outstanding is waited for (or dropped): before KeyLine arrays are unpinned, a copy must not be on its way into them.
 void REBVO::BatchGroup::dropExports() {
+    videoFlush();
     for (Export &ex : exp_of)
         if (ex.step >= 0) {
             if (ex.aos) (void)edgehip_export_wait(hip, ex.ticket);
@@ -1103,6 +1215,7 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
     if (rc == 0 && imu_mode) rc = edgehip_read_nav_imu_log(hip, (int)step, 1, navs_imu.data());
     if (rc == 0 && stereo) rc = edgehip_read_stereo_matches_log(hip, (int)step, 1, stereo_nm.data());
     if (rc == 0 && kf_track) rc = kfDrain(-1, false);
+    if (rc == 0 && step >= 1 && vx_of[(step - 1) & 3].step == step - 1) rc = videoFinish(vx_of[(step - 1) & 3]);   // the frames about to be delivered
     if (rc != 0) return rc;
     const double now = detail::now_s();
     tm.records += now - tr0;
@@ -1153,6 +1266,9 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
             ob.depth_image = nullptr;
             ob.point_cloud = nullptr;
             ob.edge_map_msg = nullptr;
+            const auto vf = cf->video_frames.find(&ob);
+            ob.jpeg = cf->wantsVideo() && vf != cf->video_frames.end() && !vf->second.empty() ? vf->second.data() : nullptr;
+            ob.jpeg_size = ob.jpeg ? vf->second.size() : 0;
             if (dfill && cf->haveCallBack() && cb_depth > 1 && in_export(i)) {   // the grid of exactly the lists exported with this step
                 std::unique_ptr<DepthGrid> &gd = cf->df_grids[&ob];
                 if (!gd) gd.reset(new DepthGrid);
@@ -1190,6 +1306,8 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
         st.have_prev = true;
         st.slot_prev = slot;
     }
+    if (rc == 0) rc = videoFetch(step, mine);   // this step's streams: their copies run under the steps that follow
+    if (rc != 0) std::cout << "\nREBVO: JPEG export failed: " << edgehip_last_error() << "\n";
     if (!cb_seq.empty()) {   // (REBVO_GROUP_CB_DEPTH=1) AoS KeyLines of every member with a callback: one packing kernel, one copy per list, synchronising
         std::vector<int32_t> kn(cb_seq.size(), 0);
         rc = edgehip_download_keylines_batch(hip, slot_before, (int)cb_seq.size(), cb_seq.data(), cb_dst.data(), kn.data());
@@ -1271,6 +1389,31 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
     for (int i = 0; i < cap; i++) {   // (PipeBuffer::img, the grey image a callback may look at, is formed by the member's output thread)
         if (!deliver[i]) continue;
         REBVO *cf = seats[i].cf;
+        deliver[i]->net_packet = nullptr;
+        if (cf->params.VideoNetEnabled && deliver[i]->jpeg) {   // rebvo_third_t.cpp:189-234, without the socket
+            PipeBuffer &ob = *deliver[i];
+            if (!cf->net_ring) cf->net_ring = std::make_shared<NetPacketRing>(cf->params.EdgeMapDelay);
+            const int kn = std::max(0, std::min(ob.ef->kn, EDGEHIP_KEYLINE_MAX));
+            std::vector<net_keyline> rec((size_t)kn);
+            net_packet_hdr h{};
+            h.kline_num = copy_net_keyline(ob.ef->kl.data(), kn, nullptr, rec.data(), EDGEHIP_KEYLINE_MAX, ob.K);
+            copy_net_keyline_nextid(ob.ef->kl.data(), kn, rec.data(), EDGEHIP_KEYLINE_MAX);
+            h.km_num = ob.ef->NumMatches();
+            h.k = (float)ob.K;
+            h.max_rho = 20;   // RHO_MAX
+            h.w = cf->params.ImageSize.w;
+            h.h = cf->params.ImageSize.h;
+            h.encoder_type = cf->params.encoder_type;
+            h.jpeg_size = (int32_t)ob.jpeg_size;
+            h.nav.dt = (float)ob.dt;
+            for (int a = 0; a < 3; a++) {
+                h.nav.Pos[a] = (float)ob.nav.Pos[a]; h.nav.Pose[a] = (float)ob.nav.PoseLie[a];
+                h.nav.Vel[a] = (float)ob.nav.Vel[a]; h.nav.Rot[a] = (float)ob.nav.RotLie[a];
+            }
+            std::vector<unsigned char> &pk = cf->net_packets[&ob];   // (the ring's own packet lives until the next push only)
+            pk = cf->net_ring->push(h, rec.data(), ob.jpeg);
+            ob.net_packet = &pk;
+        }
         cf->pipe.ReleaseBuffer(1);
         if (seats[i].out_inline) {    // nobody listens: the frame passes the third player's position right here
             (void)cf->pipe.RequestBuffer(2);

@@ -541,3 +541,16 @@ bool decode_jpeg(const std::vector<unsigned char> &d, std::vector<RGB24Pixel> &o
 }
 
 }  // namespace rebvo
+
+// flat view (tests, tools; declared in rebvo/jpeg_encode.h beside the encoder's): the reader on a stream in memory
+extern "C" int rebvo_decode_jpeg(const unsigned char *data, long long len, unsigned char *rgb, long long cap, int *w, int *h) {
+    static_assert(sizeof(rebvo::RGB24Pixel) == 3, "packed RGB24");
+    std::vector<rebvo::RGB24Pixel> px;
+    unsigned uw = 0, uh = 0;
+    std::string err;
+    if (!data || len < 0 || !rebvo::decode_jpeg(std::vector<unsigned char>(data, data + len), px, uw, uh, err, nullptr)) return -1;
+    if (w) *w = (int)uw;
+    if (h) *h = (int)uh;
+    if (rgb && (long long)px.size() * 3 <= cap) memcpy(rgb, px.data(), px.size() * 3);
+    return 0;
+}

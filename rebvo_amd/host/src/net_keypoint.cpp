@@ -58,9 +58,54 @@ int copy_net_keyline_nextid(const KeyLine *from, int kn, net_keyline *to, int kl
     return j;
 }
 
+size_t build_net_packet(net_packet_hdr hdr, const net_keyline *records, const void *jpeg, unsigned char *out) {
+    const size_t nrec = hdr.kline_num > 0 ? (size_t)hdr.kline_num : 0, njpg = hdr.jpeg_size > 0 ? (size_t)hdr.jpeg_size : 0;
+    const size_t hdr_payload = sizeof(net_packet_hdr) + sizeof(net_keyline) * nrec;
+    hdr.kline_num = (int32_t)nrec;
+    hdr.jpeg_size = (int32_t)njpg;
+    hdr.data_size = (int32_t)(hdr_payload + njpg);
+    std::memcpy(out, &hdr, sizeof hdr);
+    if (nrec) std::memcpy(out + sizeof hdr, records, sizeof(net_keyline) * nrec);
+    if (njpg) std::memcpy(out + hdr_payload, jpeg, njpg);
+    return hdr_payload + njpg;
+}
+
+const std::vector<unsigned char> &NetPacketRing::push(const net_packet_hdr &hdr, const net_keyline *records, const void *jpeg) {
+    // this frame's records wait in the entry BEFORE the current one (it comes up again `delay` frames from now) ...
+    Held &rec = held[(at + held.size() - 1) % held.size()];
+    rec.rec = hdr;
+    rec.kl.assign(records, records + (hdr.kline_num > 0 ? hdr.kline_num : 0));
+    // ... and the current entry's records, written `delay` frames ago (none yet: a zeroed header), leave with this frame's picture
+    const Held &cur = held[at];
+    net_packet_hdr h = hdr;
+    h.key_num = cur.rec.key_num;
+    h.kline_num = (int32_t)cur.kl.size();
+    h.km_num = cur.rec.km_num;
+    h.k = cur.rec.k;
+    h.max_rho = cur.rec.max_rho;
+    packet.resize(sizeof(net_packet_hdr) + sizeof(net_keyline) * cur.kl.size() + (hdr.jpeg_size > 0 ? hdr.jpeg_size : 0));
+    build_net_packet(h, cur.kl.data(), jpeg, packet.data());
+    at = (at + 1) % held.size();
+    return packet;
+}
+
 }  // namespace rebvo
 
 extern "C" {
+long long rebvo_build_net_packet(const void *hdr, const void *records, const void *jpeg, unsigned char *out) {
+    rebvo::net_packet_hdr h;
+    std::memcpy(&h, hdr, sizeof h);
+    return (long long)rebvo::build_net_packet(h, (const rebvo::net_keyline *)records, jpeg, out);
+}
+void *rebvo_net_packet_ring_new(unsigned delay) { return new rebvo::NetPacketRing(delay); }
+long long rebvo_net_packet_ring_push(void *ring, const void *hdr, const void *records, const void *jpeg, unsigned char *out, long long cap) {
+    rebvo::net_packet_hdr h;
+    std::memcpy(&h, hdr, sizeof h);
+    const std::vector<unsigned char> &p = ((rebvo::NetPacketRing *)ring)->push(h, (const rebvo::net_keyline *)records, jpeg);
+    if (out && (long long)p.size() <= cap) std::memcpy(out, p.data(), p.size());
+    return (long long)p.size();
+}
+void rebvo_net_packet_ring_free(void *ring) { delete (rebvo::NetPacketRing *)ring; }
 int rebvo_copy_net_keyline(void *keylines, int kn, const void *keylines_pair, void *out, int kl_size, double k_prof) {
     return rebvo::copy_net_keyline((rebvo::KeyLine *)keylines, kn, (const rebvo::KeyLine *)keylines_pair, (rebvo::net_keyline *)out, kl_size, k_prof);
 }

@@ -275,6 +275,12 @@ REBVO::REBVO(const char *configFile)
     // accepted and ignored (subsystems that do not exist on this path)
     config.get("Camera", "Rotate180", p.rotatedCam, false);
     config.get("REBVO", "VideoNetEnabled", p.VideoNetEnabled, false);
+    // the video half of the third thread (rebvo_third_t.cpp:104-143): the frame's encoder and the VideoSave buffer.  The socket is not rebuilt.
+    config.get("REBVO", "VideoSave", p.VideoSave, false);
+    config.get("REBVO", "VideoSaveFile", p.VideoSaveFile, false);
+    config.get("REBVO", "VideoSaveBuffersize", p.VideoSaveBuffersize, false);
+    config.get("REBVO", "EdgeMapDelay", p.EdgeMapDelay, false);
+    config.get("REBVO", "EncoderType", p.encoder_type, false);
     // src/rebvo/rebvo.cpp:153-157.  Upstream makes KFSavePercent mandatory beside TrackKeyFrames = 1; here a config without it keeps
     // loading, as it did while the key was ignored: KFSavePercent stays 0, with which the criterion never holds (the first key frame only)
     if (config.get("REBVO", "TrackKeyFrames", p.TrackKeyFrames, false) && p.TrackKeyFrames)
@@ -336,6 +342,11 @@ void REBVO::construct() {
     if (!InitOK) return;
     cam = cam_model({params.pp_x, params.pp_y}, {params.z_f_x, params.z_f_y}, params.kc, params.ImageSize);
     if (params.ImageSize.w == 0 || params.ImageSize.h == 0) { InitOK = false; return; }
+    if (params.encoder_type != 0 && params.encoder_type != 1) {   // VIDEO_ENCODER_TYPE_RAW, _MJPEG; 2 is the Exynos MFC hardware encoder
+        std::cout << "REBVO: EncoderType " << params.encoder_type << " is not available (0 = raw frames, 1 = MJPEG; the MFC encoder, 2, needs its V4L2 device)\n";
+        InitOK = false;
+        return;
+    }
     switch (params.ImuMode) {   // IMU grabber (src/rebvo/rebvo.cpp:248-281)
     case 1:   // the application pushes samples (pushIMU)
         imu = new ImuGrabber(params.CircBufferSize, params.SampleTime);
