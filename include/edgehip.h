@@ -20,6 +20,7 @@
  */
 #ifndef EDGEHIP_H
 #define EDGEHIP_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -1092,6 +1093,59 @@ int edgehip_jpeg_export_wait(edgehip_ctx *ctx, int ticket);
  * are 32-bit: about 320 megapixels; EDGEHIP_ERR_ARG beyond, as in edgehip_jpeg_enable); needs no store.  The images are done on return. */
 int edgehip_jpeg_encode_images(edgehip_ctx *ctx, const void *rgb24_dev, int w, int h, int count, int quality, void *out_dev, uint32_t cap,
                                void *sizes_dev);
+
+/* ---- baseline JPEG frames decoded on the device (MJPEG ingest; jpeg_decode.hip) ------------------------------------
+ * The counterpart of the encoder above: a camera's JPEG crosses the bus instead of its pixels and is decoded into the slot's own frame
+ * storage, with the host reader's (libjpeg's) pixel values: Huffman decoding, jpeg_idct_islow, fancy upsampling, ycc_rgb_convert, in
+ * integers only.  Decodable on the device: SOF0 / SOF1, 8-bit, one scan over every component, grey or YCbCr 4:4:4 / 4:2:2 (h2v1) /
+ * 4:2:0 (h2v2), any DHT tables, any restart interval.  Everything else gets a reason code (rebvo/jpeg_decode.h: 1 truncated header or
+ * not a JPEG, 2 progressive, 3 lossless / hierarchical / arithmetic, 4 not 8-bit, 5 neither 1 nor 3 components, 6 sampling, 7 more than
+ * one scan, 8 not YCbCr, 9 a missing or invalid table, 10 a malformed segment, 11 not the expected size, 12 longer than cap_bytes). */
+#define EDGEHIP_FRAME_RGB24 0
+#define EDGEHIP_FRAME_GREY8 1
+#define EDGEHIP_JPEG_REASON_WALK 100 /* edgehip_jpeg_decode_images: reason 100 + s, the entropy walk ended with status s */
+typedef struct edgehip_jpeg_info {
+    int32_t w, h, components, hsamp, vsamp; /* the first component's sampling factors: (1,1), (2,1) or (2,2) when decodable */
+    int32_t restart_interval;
+    uint32_t entropy_offset, entropy_length; /* the entropy-coded segment: behind the scan header, up to the first marker but RSTn */
+    int32_t reason;                          /* 0: decodable on the device */
+} edgehip_jpeg_info;
+/* Parses the stream's markers up to its scan (host only, no context).  Returns 0 with info->reason set; EDGEHIP_ERR_ARG for info == NULL. */
+int edgehip_jpeg_probe(const uint8_t *data, size_t len, edgehip_jpeg_info *info);
+/* Room for max_streams (<= nseq) compressed frames per call, cap_bytes of entropy-coded data each: page-locked and device regions,
+ * descriptors, coefficient (2 B) and sample (1 B) planes per padded sample of any sampling of the context's frame, and status words.
+ * cap_bytes == 0 frees it.  EDGEHIP_ERR_MEMORY when an allocation fails (the decoder is then off; the context stays usable).  A context
+ * that never calls this allocates and launches nothing new. */
+int edgehip_jpeg_decode_enable(edgehip_ctx *ctx, int max_streams, uint32_t cap_bytes);
+/* data[count] / len[count]: one JPEG per sequence seq_first .. seq_first + count - 1, into `slot`'s own storage as RGB24
+ * (EDGEHIP_FRAME_RGB24) or, when every stream has one component, as the 8-bit plane (EDGEHIP_FRAME_GREY8: what edgehip_upload_grey8
+ * leaves; a colour stream is EDGEHIP_ERR_ARG).  All or nothing: the headers are parsed on the host first, and if any stream is not
+ * decodable on the device — including one that is not the context's w x h or whose entropy-coded segment exceeds cap_bytes — nothing is
+ * enqueued, slot and storage stay as they were, reason_out[count] (or NULL) says why per stream and the call returns EDGEHIP_ERR_ARG:
+ * decode on the host and use the raw upload.  Otherwise the segments and descriptors go up asynchronously on the upload stream and the
+ * kernels run there, ordered like edgehip_upload_rgb_pinned: behind the slot's last use, ahead of the slot's stage A.  The caller's
+ * buffers are free on return.  A corrupt or short segment is found on the device: see edgehip_read_jpeg_decode_status.
+ * EDGEHIP_ERR_STATE when the decoder is off. */
+int edgehip_upload_jpeg(edgehip_ctx *ctx, int slot, const uint8_t *const *data, const size_t *len, int seq_first, int count, int format,
+                        int32_t *reason_out /* or NULL */);
+/* status[nseq]: per sequence, how the entropy walk of the slot's last compressed upload ended — 0 complete, 1 invalid code, 2 out of
+ * data, 3 a DC or coefficient outside the range the host reader accepts, 4 a run past the block's end (the largest over the stream's
+ * restart-interval groups).  A stream with a nonzero status leaves unspecified pixels in its own frame; the others are untouched.
+ * Synchronises the upload stream. */
+int edgehip_read_jpeg_decode_status(edgehip_ctx *ctx, int slot, int32_t *status);
+/* Measurement (tools/jpeg_decode_timing.py): device time of the three kernels of the last edgehip_upload_jpeg (entropy walk, inverse
+ * DCT, pixels) in milliseconds, and the bytes its two host-to-device copies moved (segments padded to 16 bytes, descriptors).  The
+ * events are recorded only for an upload made under edgehip_profile_enable(ctx, 1): EDGEHIP_ERR_STATE otherwise.  Waits for them. */
+int edgehip_jpeg_decode_ms(edgehip_ctx *ctx, float ms[3], uint64_t *bytes_moved /* or NULL */);
+/* The stage-level, geometry-free entry, counterpart of edgehip_jpeg_encode_images: `count` streams of one size w x h >= 1 x 1, image i as
+ * packed RGB24 to rgb24_dev_out + i * w * h * 3 (device memory, any alignment; nothing outside count * w * h * 3 bytes is written).
+ * Needs no edgehip_jpeg_decode_enable; done on return.  EDGEHIP_ERR_ARG with reason_out[count] (or NULL) filled when a stream is not
+ * decodable or not w x h (nothing is written then), or when a walk ended with status s (reason 100 + s; that image is unspecified). */
+int edgehip_jpeg_decode_images(edgehip_ctx *ctx, const uint8_t *const *data, const size_t *len, int count, int w, int h, void *rgb24_dev_out,
+                               int32_t *reason_out /* or NULL */);
+/* The slot's own frame storage of sequence `seq` as it stands: w * h * 3 bytes RGB24 or w * h bytes 8-bit mono, *format (or NULL) says
+ * which.  Synchronises.  EDGEHIP_ERR_STATE for a slot bound to a frame pool. */
+int edgehip_download_frame(edgehip_ctx *ctx, int seq, int slot, uint8_t *out, int *format);
 
 /* ---- measurement ------------------------------------------------------------------------------------- */
 /* Names of the kernel groups timed by the built-in HIP-event profiler, and their accumulated device time.

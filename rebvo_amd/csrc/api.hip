@@ -311,6 +311,32 @@ __global__ void k_gather_frames(const uint4 *__restrict__ pool, const int32_t *_
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < frame_vec; i += (size_t)gridDim.x * blockDim.x) d[i] = src[i];
 }
 
+// the slot's frames come from its own storage again (after edgehip_bind_rgb_indexed), as RGB24 (grey8 = false) or 8-bit mono (grey8 = true)
+void unbind_rgb(edgehip_ctx *c, int slot, bool grey8) {
+    edgehip_ctx::SlotSrc &ss = c->slot_src[slot];
+    if (ss.base || ss.grey8 != grey8) drop_frame_graphs(c);   // the frame source and its format are kernel arguments / choices
+    ss.base = nullptr;
+    ss.host_idx.clear();
+    ss.grey8 = grey8;
+}
+int ensure_grey8(edgehip_ctx *c) {
+    if (c->grey8) return 0;
+    void *q = nullptr;
+    const size_t bytes = (size_t)c->plan.nslots * c->plan.nseq * c->plan.n;
+    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("grey8 frame storage alloc failed"); return EDGEHIP_ERR_MEMORY; }
+    c->grey8 = (uint8_t *)q;
+    return 0;
+}
+
+// On the upload stream a copy may start once the last frame that was processed in the slot is done (nothing reads a slot's frame
+// storage after its own stage A).
+int upload_waits_for_slot(edgehip_ctx *c, int slot) {
+    if (c->rig.enabled && slot == c->rig.slot_pair && c->rig_a_valid) EH_CHECK(hipStreamWaitEvent(c->stream_up, c->ev_a[slot], 0));   // the pair slot: free behind its own stage A
+    else if (c->slot_ring[slot] >= 0) EH_CHECK(hipStreamWaitEvent(c->stream_up, c->ev_ring[c->slot_ring[slot]], 0));
+    if (c->a_api_valid[slot]) { EH_CHECK(hipStreamWaitEvent(c->stream_up, c->ev_a[slot], 0)); c->a_api_valid[slot] = false; }
+    return 0;
+}
+
 }  // namespace edgehip
 
 using namespace edgehip;
@@ -651,6 +677,7 @@ int edgehip_destroy(edgehip_ctx *c) {
     ros_free(c);
     kf_track_free(c);
     jpeg_free(c);
+    jpeg_decode_free(c);
     CtxAllocs *mine = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_allocs_mu);
@@ -755,24 +782,6 @@ static int check_seq(edgehip_ctx *c, int seq) {
     return 0;
 }
 
-// the slot reads its own storage again (after edgehip_bind_rgb_indexed)
-// the slot's frames come from its own storage again, as RGB24 (grey8 = false) or 8-bit mono (grey8 = true)
-static void unbind_rgb(edgehip_ctx *c, int slot, bool grey8 = false) {
-    edgehip_ctx::SlotSrc &ss = c->slot_src[slot];
-    if (ss.base || ss.grey8 != grey8) drop_frame_graphs(c);   // the frame source and its format are kernel arguments / choices
-    ss.base = nullptr;
-    ss.host_idx.clear();
-    ss.grey8 = grey8;
-}
-static int ensure_grey8(edgehip_ctx *c) {
-    if (c->grey8) return 0;
-    void *q = nullptr;
-    const size_t bytes = (size_t)c->plan.nslots * c->plan.nseq * c->plan.n;
-    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); set_error("grey8 frame storage alloc failed"); return EDGEHIP_ERR_MEMORY; }
-    c->grey8 = (uint8_t *)q;
-    return 0;
-}
-
 int edgehip_upload_rgb(edgehip_ctx *c, int slot, const uint8_t *rgb24, int seq_first, int count) {
     EH_ENTER(c);
     if (int e = check_slot(c, slot)) return e;
@@ -855,9 +864,7 @@ int edgehip_upload_rgb_pinned(edgehip_ctx *c, int slot, const uint8_t *rgb24_pin
     const size_t fb = (size_t)c->plan.n * 3;
     // On the upload stream: the copy of frame k+1 runs under stage A AND stages B/C of frame k.  It may start once the
     // last frame that was processed in this slot is done (nothing reads a slot's RGB after its own stage A).
-    if (c->rig.enabled && slot == c->rig.slot_pair && c->rig_a_valid) EH_CHECK(hipStreamWaitEvent(c->stream_up, c->ev_a[slot], 0));   // the pair slot: free behind its own stage A
-    else if (c->slot_ring[slot] >= 0) EH_CHECK(hipStreamWaitEvent(c->stream_up, c->ev_ring[c->slot_ring[slot]], 0));
-    if (c->a_api_valid[slot]) { EH_CHECK(hipStreamWaitEvent(c->stream_up, c->ev_a[slot], 0)); c->a_api_valid[slot] = false; }
+    if (int e = upload_waits_for_slot(c, slot)) return e;
     EH_CHECK(hipMemcpyAsync(rgbof(c, slot) + fb * seq_first, rgb24_pinned, fb * count, hipMemcpyHostToDevice, c->stream_up));
     EH_CHECK(hipEventRecord(c->ev_up[slot], c->stream_up));
     c->up_valid[slot] = true;
@@ -894,9 +901,7 @@ int edgehip_upload_grey8_pinned(edgehip_ctx *c, int slot, const uint8_t *grey8_p
     unbind_rgb(c, slot, true);
     const size_t fb = c->plan.n;
     // on the upload stream, like edgehip_upload_rgb_pinned: the copy of frame k+1 runs under the whole of frame k
-    if (c->rig.enabled && slot == c->rig.slot_pair && c->rig_a_valid) EH_CHECK(hipStreamWaitEvent(c->stream_up, c->ev_a[slot], 0));   // the pair slot: free behind its own stage A
-    else if (c->slot_ring[slot] >= 0) EH_CHECK(hipStreamWaitEvent(c->stream_up, c->ev_ring[c->slot_ring[slot]], 0));
-    if (c->a_api_valid[slot]) { EH_CHECK(hipStreamWaitEvent(c->stream_up, c->ev_a[slot], 0)); c->a_api_valid[slot] = false; }
+    if (int e = upload_waits_for_slot(c, slot)) return e;
     EH_CHECK(hipMemcpyAsync(c->grey8 + ((size_t)slot * c->plan.nseq + seq_first) * fb, grey8_pinned, fb * count, hipMemcpyHostToDevice, c->stream_up));
     EH_CHECK(hipEventRecord(c->ev_up[slot], c->stream_up));
     c->up_valid[slot] = true;

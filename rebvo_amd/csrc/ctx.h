@@ -589,6 +589,9 @@ struct edgehip_ctx {
     // edgehip_jpeg_enable: every sequence's frame as a baseline JPEG, its size records, tables and header (jpeg_encode.hip); null when off
     struct JpegStore;
     JpegStore *jpeg = nullptr;
+    // edgehip_jpeg_decode_enable: compressed regions, descriptors, coefficient and sample planes of the JPEG decoder (jpeg_decode.hip); null when off
+    struct JpegDec;
+    JpegDec *jpegdec = nullptr;
 };
 
 namespace edgehip {
@@ -712,6 +715,12 @@ bool net_store(edgehip_ctx *c, const uint8_t **records, const edgehip_net_header
 void surface_views_free(edgehip_ctx *c);            // surface_integrate.hip
 void ros_free(edgehip_ctx *c);                      // ros_edgemap.hip: the stores, edgehip_destroy
 void jpeg_free(edgehip_ctx *c);                     // jpeg_encode.hip: edgehip_jpeg_enable(ctx, q, 0, NULL), edgehip_destroy
+void jpeg_decode_free(edgehip_ctx *c);              // jpeg_decode.hip: edgehip_jpeg_decode_enable(ctx, n, 0), edgehip_destroy
+// api.hip, shared by the uploads on the upload stream: the slot reads its own storage again (RGB24 or 8-bit mono); the 8-bit storage
+// exists; stream_up waits for the last use of the slot's frame storage
+void unbind_rgb(edgehip_ctx *c, int slot, bool grey8 = false);
+int ensure_grey8(edgehip_ctx *c);
+int upload_waits_for_slot(edgehip_ctx *c, int slot);
 void kf_track_free(edgehip_ctx *c);                 // keyframe_track.hip: edgehip_keyframe_track_enable(ctx, 0, ...), edgehip_destroy
 int kf_track_reset_enqueue(edgehip_ctx *c);         // edgehip_reset: no key frame, empty records (no-op when off)
 // keyframe_track.hip, the frame driver's hooks (only with c->kftrack): the first-key-frame rule on the old slot at the frame's begin

@@ -324,7 +324,13 @@ EXPORTS = [
     "edgehip_jpeg_bound", "edgehip_jpeg_enable", "edgehip_jpeg_encode", "edgehip_jpeg_select", "edgehip_download_jpeg",
     "edgehip_download_jpeg_batch", "edgehip_jpeg_device", "edgehip_jpeg_encode_images",
     "edgehip_jpeg_export", "edgehip_jpeg_export_sizes", "edgehip_jpeg_export_fetch", "edgehip_jpeg_export_wait",
+    "edgehip_jpeg_probe", "edgehip_jpeg_decode_enable", "edgehip_upload_jpeg", "edgehip_read_jpeg_decode_status",
+    "edgehip_jpeg_decode_images", "edgehip_download_frame", "edgehip_jpeg_decode_ms",
 ]
+FRAME_RGB24, FRAME_GREY8 = 0, 1
+JPEG_REASON_WALK = 100   # edgehip_jpeg_decode_images: reason 100 + s, the entropy walk ended with status s
+JPEG_INFO_DTYPE = np.dtype([("w", "<i4"), ("h", "<i4"), ("components", "<i4"), ("hsamp", "<i4"), ("vsamp", "<i4"), ("restart_interval", "<i4"),
+                            ("entropy_offset", "<u4"), ("entropy_length", "<u4"), ("reason", "<i4")])
 
 _lib = None
 
@@ -363,6 +369,25 @@ def build_undistort_map(params):
 def jpeg_bound(w, h, comment_len=0):
     """edgehip_jpeg_bound: no JPEG stream of a w x h frame is longer (host only)."""
     return int(load_library().edgehip_jpeg_bound(int(w), int(h), C.c_uint32(int(comment_len))))
+
+
+def jpeg_probe(stream):
+    """edgehip_jpeg_probe: the stream's header as a dict (w, h, components, hsamp, vsamp, restart_interval, entropy_offset,
+    entropy_length, reason; reason 0: decodable on the device).  Host only."""
+    buf = np.frombuffer(bytes(stream), np.uint8) if not isinstance(stream, np.ndarray) else np.ascontiguousarray(stream, np.uint8)
+    info = np.zeros((), JPEG_INFO_DTYPE)
+    rc = load_library().edgehip_jpeg_probe(C.c_void_p(buf.ctypes.data if buf.size else None), C.c_size_t(buf.size), C.c_void_p(info.ctypes.data))
+    if rc != 0:
+        raise EdgeHipError(f"edgehip_jpeg_probe: {rc}")
+    return {k: int(info[k]) for k in JPEG_INFO_DTYPE.names}
+
+
+def _stream_args(streams):
+    """[bytes-like] -> (arrays kept alive, uint8 *data[count], size_t len[count])"""
+    keep = [np.ascontiguousarray(np.frombuffer(bytes(b), np.uint8) if not isinstance(b, np.ndarray) else b, np.uint8) for b in streams]
+    data = (C.c_void_p * len(keep))(*[a.ctypes.data if a.size else None for a in keep])
+    size = (C.c_size_t * len(keep))(*[a.size for a in keep])
+    return keep, data, size
 
 
 def _dp(a):
@@ -1483,6 +1508,65 @@ class EdgeHip:
                                                      C.c_uint32(cap), C.c_void_p(rec.data_ptr())))
         out, rec = out.cpu().numpy(), rec.cpu().numpy()
         return [(o[:min(int(r[0]), cap)].copy(), int(r[0]), bool(r[1])) for o, r in zip(out, rec)]
+
+    # ---- baseline JPEG frames decoded on the device (MJPEG ingest) ----
+    jpeg_probe = staticmethod(jpeg_probe)
+
+    def jpeg_decode_enable(self, max_streams=None, cap_bytes=None):
+        """edgehip_jpeg_decode_enable: room for max_streams (None: nseq) compressed frames of cap_bytes each per upload_jpeg
+        (None: w * h bytes; 0 frees it)."""
+        cap = self.w * self.h if cap_bytes is None else int(cap_bytes)
+        self._ck(self.lib.edgehip_jpeg_decode_enable(self.ctx, int(self.nseq if max_streams is None else max_streams), C.c_uint32(cap)))
+
+    def upload_jpeg(self, slot, streams, seq_first=0, fmt=FRAME_RGB24):
+        """edgehip_upload_jpeg: one JPEG per sequence from seq_first on, decoded into the slot's own storage (in-stream).  Raises
+        EdgeHipError with .reasons (per stream) when a stream is not decodable on the device: nothing was enqueued then."""
+        keep, data, size = _stream_args(streams)
+        reasons = np.zeros(len(keep), np.int32)
+        rc = self.lib.edgehip_upload_jpeg(self.ctx, int(slot), data, size, int(seq_first), len(keep), int(fmt), reasons.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            err = EdgeHipError(f"edgehip error {rc}: {self.lib.edgehip_last_error().decode()}")
+            err.code, err.reasons = rc, reasons.tolist()
+            raise err
+
+    def jpeg_decode_status(self, slot):
+        """edgehip_read_jpeg_decode_status -> int32 [nseq]: how the entropy walk of the slot's last upload_jpeg ended per sequence."""
+        st = np.zeros(self.nseq, np.int32)
+        self._ck(self.lib.edgehip_read_jpeg_decode_status(self.ctx, int(slot), st.ctypes.data_as(C.c_void_p)))
+        return st
+
+    def jpeg_decode_ms(self):
+        """edgehip_jpeg_decode_ms -> (entropy walk, inverse DCT, pixels) device milliseconds and the bytes moved of the last upload_jpeg,
+        which must have been made under profile_enable()."""
+        ms, moved = (C.c_float * 3)(), C.c_uint64(0)
+        self._ck(self.lib.edgehip_jpeg_decode_ms(self.ctx, ms, C.byref(moved)))
+        return tuple(float(v) for v in ms) + (int(moved.value),)
+
+    def jpeg_decode_images(self, streams, w, h, out=None, offset=0):
+        """edgehip_jpeg_decode_images: streams of one size -> (count, h, w, 3) uint8.  out: a torch uint8 tensor on the context's
+        device that takes the images from byte `offset` on (returned as it is, whole).  Raises EdgeHipError with .reasons."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        keep, data, size = _stream_args(streams)
+        nb = len(keep) * int(w) * int(h) * 3
+        t = torch.zeros(nb, dtype=torch.uint8, device=dev) if out is None else out
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.device == dev and t.numel() >= offset + nb
+        torch.cuda.synchronize(dev)   # the tensor was made on torch's stream, the decoder runs on the context's
+        reasons = np.zeros(len(keep), np.int32)
+        rc = self.lib.edgehip_jpeg_decode_images(self.ctx, data, size, len(keep), int(w), int(h), C.c_void_p(t.data_ptr() + int(offset)),
+                                                 reasons.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            err = EdgeHipError(f"edgehip error {rc}: {self.lib.edgehip_last_error().decode()}")
+            err.code, err.reasons = rc, reasons.tolist()
+            raise err
+        return t.cpu().numpy().reshape(len(keep), int(h), int(w), 3) if out is None else t
+
+    def download_frame(self, seq, slot):
+        """edgehip_download_frame: the slot's own frame storage of `seq` -> (h, w, 3) RGB24 or (h, w) 8-bit mono, whichever it holds."""
+        out = np.zeros(self.h * self.w * 3, np.uint8)
+        fmt = C.c_int(0)
+        self._ck(self.lib.edgehip_download_frame(self.ctx, int(seq), int(slot), C.c_void_p(out.ctypes.data), C.byref(fmt)))
+        return out[:self.h * self.w].reshape(self.h, self.w).copy() if fmt.value == FRAME_GREY8 else out.reshape(self.h, self.w, 3)
 
     def download_plane(self, seq, which):
         idx = {"img0": 0, "img1": 1, "dog": 2, "dx": 3, "dy": 4}[which]

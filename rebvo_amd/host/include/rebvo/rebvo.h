@@ -286,6 +286,9 @@ struct REBVOParameters {
     // extension: frames whose pixels all have R = G = B (a mono camera's, tripled to fit the RGB24 surface) cross PCIe as their 8-bit
     // plane when every frame of a step is such a frame (&GPU MonoUpload, default 1; src/mono_pack.cpp, batch_group.cpp)
     bool GpuMonoUpload = true;
+    // (mirror only) &GPU CompressedUpload, default 0: frames given to REBVO::pushCustomCamJpeg by an object on the group engine cross the
+    // bus compressed and are decoded on the device (edgehip_upload_jpeg) in every step whose frames are all device-decodable JPEGs
+    bool GpuCompressedUpload = false;
     // &GPU TrackerPrecision (64, or 32): which instantiation of the tracker the device runs — global_tracker::Minimizer_RV<double> (the x86
     // reference, rebvo_second_t.cpp:346) or Minimizer_RV<float> (what a USE_NE10 build of the reference runs, :339-343) — the run-time form of
     // the reference's compile-time switch (edgehip_set_tracker_precision).  ImuMode 0 only; members of a batch group must agree.
@@ -427,6 +430,10 @@ struct CustomCamPipeBuffer {
     std::shared_ptr<Image<RGB24Pixel>> img;
     double timestamp = 0;
     bool save_kf = false;   // (mirror only) REBVO::saveKeyframes when the frame was handed over: the frame is tracked with that flag
+    // (mirror only) REBVO::pushCustomCamJpeg with &GPU CompressedUpload: the frame as the camera compressed it, which the device decodes
+    // (jpeg_ok); img holds its pixels only once the host reader has been asked for them (jpeg_pixels)
+    std::vector<uint8_t> jpeg;
+    bool jpeg_ok = false, jpeg_pixels = false;
 };
 }  // namespace customCam
 
@@ -602,9 +609,16 @@ public:
         if (!(*ccpb).img) (*ccpb).img = std::make_shared<Image<RGB24Pixel>>(params.ImageSize);   // (an object on the group engine outside Init()..CleanUp(): no ring yet)
         ptr = (*ccpb).img;
         (*ccpb).timestamp = time_stamp;
+        (*ccpb).jpeg_ok = false;
         cam_cur = ccpb;
         return true;
     }
+    // (mirror only) One camera frame as a JPEG (a USB or network camera's MJPEG).  With &GPU CompressedUpload = 1 on the group engine
+    // a baseline stream the device decodes enters the camera ring as bytes; a step goes up through edgehip_upload_jpeg when every
+    // running member's frame is such a stream, any other step decodes them with the host reader and goes up as today.  Otherwise (the key
+    // off, an object of its own, a progressive / multi-scan / ... file) the frame is decoded here, on the caller's thread, and nothing
+    // else changes.  false: no buffer within timeout_secs, or a stream the host reader refuses or of another size (nothing is pushed).
+    bool pushCustomCamJpeg(const uint8_t *data, size_t len, double time_stamp, double timeout_secs = 0);
     void releaseCustomCamBuffer() {
         if (cam_cur) cam_cur->save_kf = saveKeyframes;
         if (group && cam_cur) groupFrameWritten(cam_cur);   // (a mono frame's 8-bit plane, on this thread: src/mono_pack.cpp)

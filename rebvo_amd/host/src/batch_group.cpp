@@ -50,11 +50,13 @@
 
 #include "edgehip.h"
 #include "rebvo/datasetcam.h"
+#include "rebvo/jpeg_decode.h"
 #include "rebvo/net_keypoint.h"
 #include "rebvo/rebvo.h"
 #include "rebvo_internal.h"
 
 extern "C" int rebvo_pack_mono(const uint8_t *rgb, size_t npix, uint8_t *grey);   // mono_pack.cpp
+extern "C" int rebvo_decode_jpeg(const unsigned char *data, long long len, unsigned char *rgb, long long cap, int *w, int *h);   // jpeg_reader.cpp
 
 namespace rebvo {
 
@@ -79,6 +81,7 @@ public:
         uint8_t mono_of[CCAMBUFSIZE] = {};   // per ring entry: the frame in it is mono and its 8-bit plane is in grey_ring (written by the
                                              // application's thread before it releases the entry, read by the group thread after it took it)
         bool mono = false;         // ... of the gathered frame
+        bool jpeg = false;         // the gathered frame came through pushCustomCamJpeg as bytes the device decodes (CompressedUpload)
         // With an output callback (or a pending snapshot) PipeBuffer::imgc must hold the frame.  The application's thread copies it
         // into side_img[ring entry] when it releases the camera buffer, and the group thread SWAPS that image into the step's
         // PipeBuffer (1 MB per member and step that the group thread used to copy itself).
@@ -138,6 +141,17 @@ public:
     size_t grey_bytes = 0;
     uint8_t *pair_ring = nullptr, *pair_grey_ring = nullptr;   // the same two rings for the members' pair cameras (StereoAvaiable)
     long mono_steps = 0;           // steps that went up as 8-bit planes
+    long jpeg_steps = 0;           // steps that went up compressed (edgehip_upload_jpeg)
+    int jpeg_state = 0;            // the context's decoder: 0 not asked for yet, 1 enabled, -1 refused (every step falls back)
+    // the host reader on a frame that arrived as bytes, into the frame's own image (once): a step that falls back, a listener's imgc
+    void jpegPixels(Seat &st) {
+        customCam::CustomCamPipeBuffer *b = st.cbuf;
+        if (!b || !b->jpeg_ok || b->jpeg_pixels) return;
+        int w = 0, h = 0;
+        if (rebvo_decode_jpeg(b->jpeg.data(), (long long)b->jpeg.size(), reinterpret_cast<unsigned char *>(b->img->Data()), (long long)frame_bytes, &w, &h) != 0)
+            std::cout << "REBVO(hip): a compressed frame the host reader refuses; the buffer's last pixels are tracked\n";
+        b->jpeg_pixels = true;
+    }
     long newest = -1;              // newest step enqueued
     // where the group thread's time goes (REBVO_GROUP_TIMING=1 prints it when the thread ends)
     struct Timing { double gather = 0, upload = 0, process = 0, buffers = 0, ahead = 0, held = 0, records = 0, handoff = 0; long steps = 0, ahead_hits = 0; } tm;
@@ -545,6 +559,35 @@ void REBVO::groupFrameWritten(customCam::CustomCamPipeBuffer *b, bool pair) {
     }
 }
 
+bool REBVO::pushCustomCamJpeg(const uint8_t *data, size_t len, double time_stamp, double timeout_secs) {
+    if (!data || len == 0) return false;
+    const size_t fb = (size_t)params.ImageSize.w * params.ImageSize.h * 3;
+    if (group && params.GpuCompressedUpload) {
+        jpegdec::Stream s;
+        jpegdec::parse(data, len, s);
+        if (jpegdec::expect(s, (int)params.ImageSize.w, (int)params.ImageSize.h, (uint32_t)(fb / 3)) == 0) {
+            std::shared_ptr<Image<RGB24Pixel>> ptr;
+            if (!requestCustomCamBuffer(ptr, time_stamp, timeout_secs)) return false;
+            cam_cur->jpeg.assign(data, data + len);   // the frame enters the ring as bytes; nothing is decoded on this thread
+            cam_cur->jpeg_ok = true;
+            cam_cur->jpeg_pixels = false;
+            cam_cur->save_kf = saveKeyframes;
+            cam_cur = nullptr;
+            cam_pipe.ReleaseBuffer(0);
+            return true;
+        }
+    }
+    // on the host, before a buffer is taken: a stream the reader refuses pushes nothing
+    std::vector<uint8_t> px(fb);
+    int w = 0, h = 0;
+    if (rebvo_decode_jpeg(data, (long long)len, px.data(), (long long)fb, &w, &h) != 0 || w != (int)params.ImageSize.w || h != (int)params.ImageSize.h) return false;
+    std::shared_ptr<Image<RGB24Pixel>> ptr;
+    if (!requestCustomCamBuffer(ptr, time_stamp, timeout_secs)) return false;
+    std::memcpy(ptr->Data(), px.data(), fb);
+    releaseCustomCamBuffer();
+    return true;
+}
+
 // ---- the group's tracker thread -------------------------------------------------------------------------------------------
 // Page-lock (or release) the KeyLine arrays of a member's PipeBuffers.  A range the driver refuses stays pageable: the lists then
 // come through the library's staging buffer as before.
@@ -828,6 +871,8 @@ bool REBVO::BatchGroup::gather(bool block, bool &any_running, bool &any_leaving)
                 st.ring_idx = -1;
                 st.ring_idx = ringEntryOf(reinterpret_cast<const uint8_t *>(cb->img->Data()));
                 st.mono = grey_ring && st.ring_idx >= 0 && st.mono_of[st.ring_idx] != 0;
+                st.jpeg = cb->jpeg_ok;
+                if (st.jpeg) st.mono = false;   // (the entry's 8-bit plane is an earlier frame's)
             }
             if (stereo && st.cbuf && !st.cbuf_pair) {   // one pair frame per accepted main frame, no drop logic (rebvo_first_t.cpp:183-199)
                 customCam::CustomCamPipeBuffer *pb = cf->cam_pipe_stereo.RequestBufferTimeoutable(1, block && !waited ? 0.001 : 0.0);
@@ -866,6 +911,30 @@ int REBVO::BatchGroup::uploadRuns(int slot, bool pair) {
     int rc = 0;
     uint8_t *const grey_r = pair ? pair_grey_ring : grey_ring;
     auto idx_of = [&](const Seat &st) { return pair ? st.pair_idx : st.ring_idx; };
+    if (!pair) {   // CompressedUpload: the step goes up as JPEG when EVERY running member's frame is a device-decodable stream (as all_mono below)
+        bool any = false, all = true;
+        for (const Seat &st : seats)
+            if (st.running) { any = any || st.jpeg; all = all && st.jpeg; }
+        if (any && all && jpeg_state == 0)
+            jpeg_state = edgehip_jpeg_decode_enable(hip, cap, (uint32_t)(frame_bytes / 3)) == 0 ? 1 : -1;
+        if (any && all && jpeg_state == 1) {
+            std::vector<const uint8_t *> data;
+            std::vector<size_t> len;
+            for (int i = 0; i < cap && rc == 0;) {
+                if (!seats[i].running) { i++; continue; }
+                data.clear(); len.clear();
+                int n = 0;
+                for (; i + n < cap && seats[i + n].running; n++) { data.push_back(seats[i + n].cbuf->jpeg.data()); len.push_back(seats[i + n].cbuf->jpeg.size()); }
+                rc = edgehip_upload_jpeg(hip, slot, data.data(), len.data(), i, n, EDGEHIP_FRAME_RGB24, nullptr);
+                i += n;
+            }
+            if (rc == 0) jpeg_steps++;
+            return rc;
+        }
+        if (any)   // a mixed step (or no decoder): the compressed members' pixels from the host reader, then everything as today
+            for (Seat &st : seats)
+                if (st.running && st.jpeg) jpegPixels(st);
+    }
     // a step whose frames are ALL mono goes up as 8-bit planes (a third of the bytes; the slot's format is one per step)
     bool all_mono = grey_r != nullptr;
     for (const Seat &st : seats) all_mono = all_mono && (!st.running || (pair ? st.pair_mono : st.mono));
@@ -936,6 +1005,8 @@ int REBVO::BatchGroup::launch(long step, const std::vector<double> &ts) {
         nb.dtp1 = tp0;   // start of the step; complete() turns it into the step's duration
         if (imu_mode) nb.imu = st.imu_data;
         nb.imgc_valid = false;
+        const bool listened = cf->haveCallBack() || cf->saveImg;
+        if (st.jpeg && (listened || (cf->wantsVideo() && cf->params.encoder_type == 0))) jpegPixels(st);   // imgc / the raw video frame: by the host reader, only now
         if (cf->wantsVideo()) {
             std::vector<uint8_t> &v = cf->video_frames[&nb];
             v.clear();   // (EncoderType 1: filled by videoFetch when this step completes)
@@ -944,7 +1015,6 @@ int REBVO::BatchGroup::launch(long step, const std::vector<double> &ts) {
                 videoAppend(cf, v.data(), v.size());
             }
         }
-        const bool listened = cf->haveCallBack() || cf->saveImg;
         if (st.out_inline && listened) {   // somebody listens now: from here on this member has its output thread
             st.out_inline = false;
             st.out_thread = std::thread(ThirdThread, cf);
@@ -953,7 +1023,7 @@ int REBVO::BatchGroup::launch(long step, const std::vector<double> &ts) {
             cf->ensureHostViews(nb, false);
             nb.imgc_valid = true;   // the output thread converts / saves only a frame that was really kept (a request that arrives after the
                                     // launch is honoured by the first later frame launched with it pending)
-            if (st.ring_idx >= 0 && st.side_ok[st.ring_idx]) {   // the application's thread made the copy: take it
+            if (!st.jpeg && st.ring_idx >= 0 && st.side_ok[st.ring_idx]) {   // the application's thread made the copy: take it
                 std::swap(nb.imgc, st.side_img[st.ring_idx]);
                 st.side_ok[st.ring_idx] = 0;
             } else {
@@ -1525,9 +1595,9 @@ void REBVO::BatchGroup::threadMain() {
     if (getenv("REBVO_GROUP_TIMING") && tm.steps > 0) {
         const double k = 1e6 / tm.steps;
         std::printf("REBVO(hip) group '%s': %ld steps (%ld as 8-bit planes), look-ahead copies %ld; us per step on the group thread: gather %.0f, upload calls %.0f, "
-                    "process_frame %.0f, PipeBuffers %.0f, look-ahead %.0f, wait for the copy + release %.0f, wait for the records %.0f, hand-off %.0f\n",
+                    "process_frame %.0f, PipeBuffers %.0f, look-ahead %.0f, wait for the copy + release %.0f, wait for the records %.0f, hand-off %.0f; %ld steps went up compressed\n",
                     name.c_str(), tm.steps, mono_steps, tm.ahead_hits, tm.gather * k, tm.upload * k, tm.process * k, tm.buffers * k, tm.ahead * k, tm.held * k,
-                    tm.records * k, tm.handoff * k);
+                    tm.records * k, tm.handoff * k, jpeg_steps);
         if (atoi(getenv("REBVO_GROUP_TIMING")) > 1)
             for (size_t j = tlog.size() > 12 ? tlog.size() - 12 : 0; j < tlog.size(); j++)
                 std::printf("  step %2zu: launch %8.0f..%8.0f  look-ahead copy issued %8.0f  this step's copy done %8.0f  records of step-2 read %8.0f  (us)\n", j,

@@ -315,6 +315,8 @@ REBVO::REBVO(const char *configFile)
     {
         int mono = 1;
         if (config.get("GPU", "MonoUpload", mono, false)) p.GpuMonoUpload = mono != 0;
+        int compressed = 0;
+        if (config.get("GPU", "CompressedUpload", compressed, false)) p.GpuCompressedUpload = compressed != 0;
         int tprec = 64;
         if (config.get("GPU", "TrackerPrecision", tprec, false)) p.GpuTrackerPrecision = tprec;
     }
