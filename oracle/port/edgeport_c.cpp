@@ -256,7 +256,17 @@ bool ext_rot_vel(const Ctx &c, Slot &s, const double vel[3], double Wx[36], doub
             JtF[a] += phi[a] * y;
         }
     }
-    svd6_solve_pinv(JtJ, JtF, X, Rx);
+    bool finite = true;
+    for (int i = 0; i < 36; i++) finite = finite && std::isfinite(JtJ[i]);
+    if (finite) {
+        svd6_solve_pinv(JtJ, JtF, X, Rx);
+    } else {
+        // LAPACK's dgesvd_ (behind TooN::SVD<>) answers a matrix that holds an infinity or a NaN with NaN singular values and vectors, and
+        // TooN inverts those to NaN: X and Rx are NaN throughout.  The Jacobi solve would stop at once on such a matrix and, with an
+        // infinite diagonal entry, drop every singular value: Rx = 0.
+        for (int i = 0; i < 36; i++) Rx[i] = NAN;
+        for (int i = 0; i < 6; i++) X[i] = NAN;
+    }
     for (int i = 0; i < 36; i++) Wx[i] = JtJ[i];
     for (int i = 0; i < 36; i++) if (std::isnan(Rx[i])) return false;
     for (int i = 0; i < 6; i++) if (std::isnan(X[i])) return false;

@@ -1764,6 +1764,19 @@ int edgehip_ext_rot_vel(edgehip_ctx *c, int slot, const double *vel, double loc_
             for (int b = a; b < 6; b++) { JtJ[a * 6 + b] = sum[ns]; JtJ[b * 6 + a] = sum[ns]; ns++; }
         for (int a = 0; a < 6; a++) JtF[a] = sum[ns++];
         // X = SVD(JtJ).backsub(JtF), Rx = SVD(JtJ).get_pinv() with TooN's conditioning (SVD.h:176-207, 1e9)
+        // A row at the pole 1 / rho + vel[2] == 0 (or with a NaN s_rho) leaves an infinity or a NaN in JtJ.  LAPACK's dgesvd_ answers
+        // such a matrix with NaN singular values and vectors and TooN inverts those to NaN: X and Rx are NaN throughout.  (The Jacobi
+        // sweeps would stop at once on it and, with an infinite diagonal entry, the cut would drop every eigenvalue: Rx = 0.)
+        bool finite = true;
+        for (int i = 0; i < 36; i++) finite = finite && isfinite(JtJ[i]);
+        if (!finite) {
+            for (int i = 0; i < 6; i++) X[(size_t)s * 6 + i] = NAN;
+            if (Rx)
+                for (int i = 0; i < 36; i++) Rx[(size_t)s * 36 + i] = NAN;
+            if (Wx) memcpy(Wx + (size_t)s * 36, JtJ, sizeof JtJ);
+            if (ok) ok[s] = 0;
+            continue;
+        }
         double V[36], e[6], inv[6], smax = 0;
         jacobi_eig6_host(JtJ, V, e);
         for (int i = 0; i < 6; i++) smax = fmax(smax, fabs(e[i]));
