@@ -11,6 +11,7 @@
 
 #include "ctx.h"
 #include "stage_a_dev.h"
+#include "rebvo/linalg.h"
 
 namespace edgehip {
 
@@ -153,31 +154,18 @@ static void plane_fit_pinv(int win_s, double *pinv /*[3][nn]*/) {
             Phi[k * 3 + 1] = i;
             Phi[k * 3 + 2] = 1;
         }
-    double A[3][3];
+    rebvo::la::Mat<3, 3> A;
     for (int r = 0; r < 3; r++)
         for (int cidx = 0; cidx < 3; cidx++) {
             double s = 0;
             for (int k = 0; k < nn; k++) s += Phi[k * 3 + r] * Phi[k * 3 + cidx];
-            A[r][cidx] = s;
+            A(r, cidx) = s;
         }
-    double Bm[3][3];
-    Bm[0][0] = A[2][2] * A[1][1] - A[2][1] * A[1][2];
-    Bm[0][1] = -(A[2][2] * A[0][1] - A[2][1] * A[0][2]);
-    Bm[0][2] = A[1][2] * A[0][1] - A[1][1] * A[0][2];
-    Bm[1][0] = -(A[2][2] * A[1][0] - A[2][0] * A[1][2]);
-    Bm[1][1] = A[2][2] * A[0][0] - A[2][0] * A[0][2];
-    Bm[1][2] = -(A[1][2] * A[0][0] - A[1][0] * A[0][2]);
-    Bm[2][0] = A[2][1] * A[1][0] - A[2][0] * A[1][1];
-    Bm[2][1] = -(A[2][1] * A[0][0] - A[2][0] * A[0][1]);
-    Bm[2][2] = A[1][1] * A[0][0] - A[1][0] * A[0][1];
-    // Phi^T Phi is diagonal for a symmetric window, so Gaussian elimination returns the plain product
-    const double det = A[0][0] * A[1][1] * A[2][2];
-    for (int r = 0; r < 3; r++)
-        for (int cidx = 0; cidx < 3; cidx++) Bm[r][cidx] = Bm[r][cidx] / det;
+    const rebvo::la::Mat<3, 3> Bm = rebvo::la::inv3(A);   // util::Matrix3x3Inv
     for (int r = 0; r < 3; r++)
         for (int k = 0; k < nn; k++) {
             double s = 0;
-            for (int j = 0; j < 3; j++) s += Bm[r][j] * Phi[k * 3 + j];
+            for (int j = 0; j < 3; j++) s += Bm(r, j) * Phi[k * 3 + j];
             pinv[r * nn + k] = s;
         }
 }

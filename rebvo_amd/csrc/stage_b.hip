@@ -38,8 +38,10 @@
 #include "ctx.h"
 #include "resid_carry.h"
 #include "wave_reduce.h"
+#include "rebvo/linalg.h"
 
 namespace edgehip {
+namespace la = rebvo::la;
 
 // ---------------------------------------------------------------------------------------------------
 // EstimateQuantile
@@ -656,53 +658,13 @@ __global__ __launch_bounds__(256) void k_tvr_prepare(const KlSoA *kls, const int
     resid0[(size_t)seq * cap + i] = 0.0;  // "Init residuals", global_tracker.cpp:625
 }
 
-// ---------------------------------------------------------------------------------------------------
-// SO3 exponential as TooN::SO3<>::exp + rodrigues_so3_exp (TooN so3.h:203-285)
-// ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void so3_exp_inl(const double (&w)[3], double (&R)[9]) {
-    const double one_6th = 1.0 / 6.0, one_20th = 1.0 / 20.0;
-    const double theta_sq = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    const double theta = sqrt(theta_sq);
-    double A, B;
-    if (theta_sq < 1e-8) {
-        A = 1.0 - one_6th * theta_sq;
-        B = 0.5;
-    } else if (theta_sq < 1e-6) {
-        B = 0.5 - 0.25 * one_6th * theta_sq;
-        A = 1.0 - theta_sq * one_6th * (1.0 - one_20th * theta_sq);
-    } else {
-        const double inv_theta = 1.0 / theta;
-        A = sin(theta) * inv_theta;
-        B = (1 - cos(theta)) * (inv_theta * inv_theta);
-    }
-    const double wx2 = w[0] * w[0], wy2 = w[1] * w[1], wz2 = w[2] * w[2];
-    R[0] = 1.0 - B * (wy2 + wz2);
-    R[4] = 1.0 - B * (wx2 + wz2);
-    R[8] = 1.0 - B * (wx2 + wy2);
-    double a = A * w[2], b = B * (w[0] * w[1]);
-    R[1] = b - a; R[3] = b + a;
-    a = A * w[1]; b = B * (w[0] * w[2]);
-    R[2] = b + a; R[6] = b - a;
-    a = A * w[0]; b = B * (w[1] * w[2]);
-    R[5] = b - a; R[7] = b + a;
-}
-// (out of line for the callers that are not on anybody's critical path: its arrays then live in scratch memory)
-__device__ __noinline__ void so3_exp(const double w[3], double R[9]) {
-    const double wv[3] = {w[0], w[1], w[2]};
-    double Rr[9];
-    so3_exp_inl(wv, Rr);
-    for (int i = 0; i < 9; i++) R[i] = Rr[i];
-}
-
 // Per-evaluation constants of TryVelRot (global_tracker.cpp:309-341): R0 = exp(W), RM = 2x2 block of
-// exp((0,0,W_z)), Vt = V.
+// exp((0,0,W_z)), Vt = V.  The exponential is TooN::SO3<>::exp (la::so3_exp, rebvo/linalg.h).
 __device__ __noinline__ void tvr_setup(SeqDev *sq, const double *X) {
-    double R0[9], Rz[9];
-    so3_exp(X + 3, R0);
-    const double wz[3] = {0.0, 0.0, X[5]};
-    so3_exp(wz, Rz);
-    for (int i = 0; i < 9; i++) sq->Rt[i] = R0[i];  // row-major R0(i,j)
-    sq->RM[0] = Rz[0]; sq->RM[1] = Rz[1]; sq->RM[2] = Rz[3]; sq->RM[3] = Rz[4];
+    const la::Mat<3, 3> R0 = la::so3_exp(la::Vec<3>{{X[3], X[4], X[5]}});
+    const la::Mat<3, 3> Rz = la::so3_exp(la::Vec<3>{{0.0, 0.0, X[5]}});
+    for (int i = 0; i < 9; i++) sq->Rt[i] = R0.a[i];  // row-major R0(i,j)
+    sq->RM[0] = Rz(0, 0); sq->RM[1] = Rz(0, 1); sq->RM[2] = Rz(1, 0); sq->RM[3] = Rz(1, 1);
     for (int i = 0; i < 3; i++) sq->Vt[i] = X[i];
 }
 
@@ -714,15 +676,14 @@ __device__ __noinline__ void tvr_setup(SeqDev *sq, const double *X) {
 __device__ __forceinline__ void tvr_setup2(SeqDev *sq, const double *X, const int lane, const bool zero = false, const int l0 = 0) {
     if (lane >= l0 && lane < l0 + 2) {
         const bool first = lane == l0;
-        const double wv[3] = {first ? X[3] : 0.0, first ? X[4] : 0.0, X[5]};
-        double R[9];
-        so3_exp_inl(wv, R);   // inlined: R stays in registers (through a call it is scratch memory, a round trip each way)
+        // inlined: R stays in registers (through a call it is scratch memory, a round trip each way)
+        const la::Mat<3, 3> R = la::so3_exp(la::Vec<3>{{first ? X[3] : 0.0, first ? X[4] : 0.0, X[5]}});
         double *Rt = zero ? sq->zRt : sq->Rt, *Vt = zero ? sq->zVt : sq->Vt, *RM = zero ? sq->zRM : sq->RM;
         if (first) {
-            for (int i = 0; i < 9; i++) Rt[i] = R[i];
+            for (int i = 0; i < 9; i++) Rt[i] = R.a[i];
             for (int i = 0; i < 3; i++) Vt[i] = X[i];
         } else {
-            RM[0] = R[0]; RM[1] = R[1]; RM[2] = R[3]; RM[3] = R[4];
+            RM[0] = R(0, 0); RM[1] = R(0, 1); RM[2] = R(1, 0); RM[3] = R(1, 1);
         }
     }
 }
@@ -1873,222 +1834,31 @@ void k_try_velrot2(TvrArgs a) {
 // ---------------------------------------------------------------------------------------------------
 // 6x6 linear algebra for the LM step (single lane)
 // ---------------------------------------------------------------------------------------------------
-// Symmetric eigen-decomposition by cyclic Jacobi; A = V diag(e) V^T.  Stands in for LAPACK dgesvd_ behind
-// TooN::SVD<> (for a symmetric matrix singular values = |e|, U = V*sign(e)).
-__device__ __noinline__ void jacobi_eig6(const double Ain[36], double V[36], double e[6], double *A /*[36] scratch*/) {
-#pragma nounroll
-    for (int i = 0; i < 36; i++) { A[i] = Ain[i]; V[i] = 0; }
-#pragma nounroll
-    for (int i = 0; i < 6; i++) V[i * 7] = 1;
-    for (int sweep = 0; sweep < 30; sweep++) {
-        double off = 0, diag = 0;
-#pragma nounroll
-        for (int p = 0; p < 6; p++) {
-            diag += A[p * 7] * A[p * 7];
-#pragma nounroll
-            for (int q = p + 1; q < 6; q++) off += A[p * 6 + q] * A[p * 6 + q];
-        }
-        if (!(off > 1e-32 * diag) || !(off > 0)) break;  // off-diagonal energy below fp64 roundoff of the diagonal
-#pragma nounroll
-        for (int p = 0; p < 5; p++)
-#pragma nounroll
-            for (int q = p + 1; q < 6; q++) {
-                const double apq = A[p * 6 + q];
-                if (apq == 0) continue;
-                const double theta = (A[q * 7] - A[p * 7]) / (2 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1));
-                const double c = 1 / sqrt(t * t + 1), s = t * c;
-#pragma nounroll
-                for (int k = 0; k < 6; k++) {
-                    const double akp = A[k * 6 + p], akq = A[k * 6 + q];
-                    A[k * 6 + p] = c * akp - s * akq;
-                    A[k * 6 + q] = s * akp + c * akq;
-                }
-#pragma nounroll
-                for (int k = 0; k < 6; k++) {
-                    const double apk = A[p * 6 + k], aqk = A[q * 6 + k];
-                    A[p * 6 + k] = c * apk - s * aqk;
-                    A[q * 6 + k] = s * apk + c * aqk;
-                }
-#pragma nounroll
-                for (int k = 0; k < 6; k++) {
-                    const double vkp = V[k * 6 + p], vkq = V[k * 6 + q];
-                    V[k * 6 + p] = c * vkp - s * vkq;
-                    V[k * 6 + q] = s * vkp + c * vkq;
-                }
-            }
-    }
-#pragma nounroll
-    for (int i = 0; i < 6; i++) e[i] = A[i * 7];
-}
-
-// h = SVD(A).backsub(b) with TooN's conditioning (SVD.h:176-196, 264-272; condition_no = 1e9)
-__device__ __noinline__ void svd_backsub6(const double A[36], const double b[6], double h[6], double *V, double *Awork,
-                                          double *e, double *y) {
-    jacobi_eig6(A, V, e, Awork);
-    double smax = 0;
-#pragma nounroll
-    for (int i = 0; i < 6; i++) smax = fmax(smax, fabs(e[i]));
-#pragma nounroll
-    for (int i = 0; i < 6; i++) {
-        double d = 0;
-#pragma nounroll
-        for (int k = 0; k < 6; k++) d += V[k * 6 + i] * b[k];
-        const double inv = (fabs(e[i]) * 1e9 <= smax) ? 0.0 : 1.0 / e[i];
-        y[i] = d * inv;
-    }
-#pragma nounroll
-    for (int k = 0; k < 6; k++) {
-        double d = 0;
-#pragma nounroll
-        for (int i = 0; i < 6; i++) d += V[k * 6 + i] * y[i];
-        h[k] = d;
-    }
-}
-
-// TooN::Cholesky<6> (LDL^T, Cholesky.h:88-125) and its vector backsub (:131-160)
-__device__ __noinline__ void chol6(const double A[36], double L[36]) {
-#pragma nounroll
-    for (int i = 0; i < 36; i++) L[i] = A[i];
-#pragma nounroll
-    for (int col = 0; col < 6; col++) {
-        double inv_diag = 1;
-#pragma nounroll
-        for (int row = col; row < 6; row++) {
-            double val = L[row * 6 + col];
-#pragma nounroll
-            for (int col2 = 0; col2 < col; col2++) val -= L[col2 * 6 + col] * L[row * 6 + col2];
-            if (row == col) {
-                L[row * 6 + col] = val;
-                if (val == 0) return;  // rank deficient: TooN stops here
-                inv_diag = 1 / val;
-            } else {
-                L[col * 6 + row] = val;
-                L[row * 6 + col] = val * inv_diag;
-            }
-        }
-    }
-}
-__device__ __noinline__ void chol6_backsub(const double L[36], const double v[6], double r[6], double *y) {
-#pragma nounroll
-    for (int i = 0; i < 6; i++) {
-        double val = v[i];
-#pragma nounroll
-        for (int j = 0; j < i; j++) val -= L[i * 6 + j] * y[j];
-        y[i] = val;
-    }
-#pragma nounroll
-    for (int i = 0; i < 6; i++) y[i] /= L[i * 7];
-#pragma nounroll
-    for (int i = 5; i >= 0; i--) {
-        double val = y[i];
-#pragma nounroll
-        for (int j = i + 1; j < 6; j++) val -= L[j * 6 + i] * r[j];
-        r[i] = val;
-    }
-}
-// matrix backsub of the identity: get_inverse() (Cholesky.h:165-200); note y[i] *= (1/d) here, not y[i] /= d
-__device__ __noinline__ void chol6_inverse(const double L[36], double Inv[36], double *y, double *r) {
-#pragma nounroll
-    for (int c = 0; c < 6; c++) {
-#pragma nounroll
-        for (int i = 0; i < 6; i++) {
-            double val = (i == c) ? 1.0 : 0.0;
-#pragma nounroll
-            for (int j = 0; j < i; j++) val -= L[i * 6 + j] * y[j];
-            y[i] = val;
-        }
-#pragma nounroll
-        for (int i = 0; i < 6; i++) y[i] *= (1 / L[i * 7]);
-#pragma nounroll
-        for (int i = 5; i >= 0; i--) {
-            double val = y[i];
-#pragma nounroll
-            for (int j = i + 1; j < 6; j++) val -= L[j * 6 + i] * r[j];
-            r[i] = val;
-        }
-#pragma nounroll
-        for (int i = 0; i < 6; i++) Inv[i * 6 + c] = r[i];
-    }
-}
-
-// Register-resident versions (arrays indexed only by unrolled constants) of chol6 / backsub / inverse above.
-__device__ __forceinline__ void chol6_r(const double (&A)[36], double (&L)[36]) {
+// The algebra itself is rebvo/linalg.h's (la::Cholesky<6>: TooN's L D L^T, register resident; la::SymSVD<6>: cyclic Jacobi
+// standing in for LAPACK dgesvd_ behind TooN::SVD<>).
+//
+// h = SVD(A).backsub(b) with TooN's conditioning (SVD.h:176-196, 264-272; condition_no = 1e9).  Out of line, A in and b in / h out
+// through LDS: the branch is rarely taken, and the common Cholesky path must not inherit an unrolled eigen-solve or have its
+// matrices in scratch memory because a call takes their address.
+__device__ __noinline__ void svd_backsub6(const double *A /*[36]*/, double *bh /*[6]*/) {
+    la::Mat<6, 6> Am;
+    la::Vec<6> b;
 #pragma unroll
-    for (int i = 0; i < 36; i++) L[i] = A[i];
-    bool alive = true;   // TooN returns at the first zero pivot, leaving the rest untouched
+    for (int i = 0; i < 36; i++) Am.a[i] = A[i];
 #pragma unroll
-    for (int col = 0; col < 6; col++) {
-        double inv_diag = 1;
+    for (int i = 0; i < 6; i++) b[i] = bh[i];
+    const la::Vec<6> h = la::SymSVD<6>(Am).backsub(b);
 #pragma unroll
-        for (int row = col; row < 6; row++) {
-            double val = L[row * 6 + col];
-#pragma unroll
-            for (int col2 = 0; col2 < col; col2++) val -= L[col2 * 6 + col] * L[row * 6 + col2];
-            if (row == col) {
-                if (alive) L[row * 6 + col] = val;
-                if (val == 0) alive = false;
-                inv_diag = 1 / val;
-            } else if (alive) {
-                L[col * 6 + row] = val;
-                L[row * 6 + col] = val * inv_diag;
-            }
-        }
-    }
-}
-__device__ __forceinline__ void chol6_backsub_r(const double (&L)[36], const double (&vv)[6], double (&r)[6]) {
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double val = vv[i];
-#pragma unroll
-        for (int j = 0; j < i; j++) val -= L[i * 6 + j] * y[j];
-        y[i] = val;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) y[i] /= L[i * 7];
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double val = y[i];
-#pragma unroll
-        for (int j = i + 1; j < 6; j++) val -= L[j * 6 + i] * r[j];
-        r[i] = val;
-    }
-}
-__device__ __forceinline__ void chol6_inverse_r(const double (&L)[36], double (&Inv)[36]) {
-    double invd[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) invd[i] = 1 / L[i * 7];
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-        double y[6], r[6];
-#pragma unroll
-        for (int i = 0; i < 6; i++) {
-            double val = (i == c) ? 1.0 : 0.0;
-#pragma unroll
-            for (int j = 0; j < i; j++) val -= L[i * 6 + j] * y[j];
-            y[i] = val;
-        }
-#pragma unroll
-        for (int i = 0; i < 6; i++) y[i] *= invd[i];   // y[i] *= (1/d), Cholesky.h:165-200
-#pragma unroll
-        for (int i = 5; i >= 0; i--) {
-            double val = y[i];
-#pragma unroll
-            for (int j = i + 1; j < 6; j++) val -= L[j * 6 + i] * r[j];
-            r[i] = val;
-        }
-#pragma unroll
-        for (int i = 0; i < 6; i++) Inv[i * 6 + c] = r[i];
-    }
+    for (int i = 0; i < 6; i++) bh[i] = h[i];
 }
 
 // The 6x6 solve of one LM step: h = TooN::Cholesky<6>(ApI).backsub(nb) (global_tracker.cpp:767-768) or, in the init phase,
 // h = TooN::SVD<>(ApI).backsub(nb) (:660-661, 711-712).  Shared by lm_body and edgehip_lm_solve (the parity test of the rule below).
-__device__ __forceinline__ void lm_solve6(const double (&ApI)[36], const double (&nb)[6], const bool svd_rule, double (&hh)[6],
-                                          double (*s_m)[36], double (*s_v)[6]) {
-    double L[36];
-    chol6_r(ApI, L);
+// s_m / s_v: LDS for the Jacobi branch's call.
+__device__ __forceinline__ void lm_solve6(const la::Mat<6, 6> &ApI, const la::Vec<6> &nb, const bool svd_rule, la::Vec<6> &hh,
+                                          double *s_m /*[36]*/, double *s_v /*[6]*/) {
+    const la::Cholesky<6> chol(ApI);
+    const double (&L)[36] = chol.L.a;
     bool use_svd = false;
     if (svd_rule) {
         // TooN::SVD<>::backsub zeroes singular values s_i with s_i * 1e9 <= s_max (SVD.h:264-272); when none is, the
@@ -2098,33 +1868,35 @@ __device__ __forceinline__ void lm_solve6(const double (&ApI)[36], const double 
         // cannot clear (or that is not positive definite) takes the Jacobi path, which applies TooN's rule value by value.
         // (Round 2 compared the pivot ratio with 1e7: unsound — pivots 8e9..4e3 at condition 1.7e9 — found by
         // tests/test_knife_edge_gpu.py::test_lm_solve_against_toon_either_side_of_the_svd_cutoff.)
-        double dmin = L[0], tr = ApI[0];
+        double dmin = L[0], tr = ApI.a[0];
 #pragma unroll
-        for (int i = 1; i < 6; i++) { dmin = fmin(dmin, L[i * 7]); tr += ApI[i * 7]; }
+        for (int i = 1; i < 6; i++) { dmin = fmin(dmin, L[i * 7]); tr += ApI.a[i * 7]; }
         double bound = 1;
 #pragma unroll
         for (int i = 0; i < 6; i++) bound *= tr / L[i * 7];
         use_svd = !(dmin > 0) || !(bound < 0.99e9);
     }
     if (use_svd) {
-        double *A_l = s_m[0], *b_l = s_v[0], *h_l = s_v[2] + 0;
-        for (int i = 0; i < 36; i++) A_l[i] = ApI[i];
-        for (int i = 0; i < 6; i++) b_l[i] = nb[i];
-        svd_backsub6(A_l, b_l, h_l, s_m[2], s_m[3], s_v[1], s_m[1]);
 #pragma unroll
-        for (int i = 0; i < 6; i++) hh[i] = h_l[i];
+        for (int i = 0; i < 36; i++) s_m[i] = ApI.a[i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) s_v[i] = nb[i];
+        svd_backsub6(s_m, s_v);
+#pragma unroll
+        for (int i = 0; i < 6; i++) hh[i] = s_v[i];
     } else {
-        chol6_backsub_r(L, nb, hh);
+        hh = chol.backsub(nb);
     }
 }
 
 // edgehip_lm_solve: n independent systems through lm_solve6, one wave each (lane 0 does the algebra, like k_lm_step)
 __global__ __launch_bounds__(64) void k_lm_solve(const double *__restrict__ A, const double *__restrict__ b, double *__restrict__ h,
                                                   int svd_rule) {
-    __shared__ double s_m[4][36], s_v[3][6];
+    __shared__ double s_m[36], s_v[6];
     if (threadIdx.x != 0) return;
-    double ApI[36], nb[6], hh[6];
-    for (int i = 0; i < 36; i++) ApI[i] = A[(size_t)blockIdx.x * 36 + i];
+    la::Mat<6, 6> ApI;
+    la::Vec<6> nb, hh;
+    for (int i = 0; i < 36; i++) ApI.a[i] = A[(size_t)blockIdx.x * 36 + i];
     for (int i = 0; i < 6; i++) nb[i] = b[(size_t)blockIdx.x * 6 + i];
     lm_solve6(ApI, nb, svd_rule != 0, hh, s_m, s_v);
     for (int i = 0; i < 6; i++) h[(size_t)blockIdx.x * 6 + i] = hh[i];
@@ -2287,12 +2059,11 @@ __device__ __forceinline__ void lm_body(const LmArgs &a, const int seq, const in
     // slot v adds the two group sums.
     constexpr int NCH = DUAL ? 2 : 1;
     __shared__ double s_part_[NCH][2][32];
-    __shared__ double s_m_[NCH][4][36], s_v_[NCH][3][6];  // 6x6 work matrices / vectors of the solves (LDS, not scratch)
+    __shared__ double s_m_[NCH][36], s_v_[NCH][6];  // matrix in, vector in / out of the Jacobi solve's call (LDS, not scratch)
     __shared__ double s_sum_[NCH][kNumSums];
     __shared__ double s_bl_[NCH][256];
     double (*s_part)[32] = s_part_[ch];
-    double (*s_m)[36] = s_m_[ch];
-    double (*s_v)[6] = s_v_[ch];
+    double *s_m = s_m_[ch], *s_v = s_v_[ch];
     double *s_sum = s_sum_[ch], *s_bl = s_bl_[ch];
     // the chain's locals (LDS copy of the state)
     double *cX = ch ? sq->zX : sq->X, *cXnew = ch ? sq->zXnew : sq->Xnew, *ch_h = ch ? sq->zh : sq->h;
@@ -2352,9 +2123,11 @@ __device__ __forceinline__ void lm_body(const LmArgs &a, const int seq, const in
     if (lane == 0) {
     // The serial LM logic runs on register copies of the hot state (fully unrolled 6x6 algebra): with the state
     // left in LDS every one of its ~1000 dependent accesses paid an LDS round trip (~25 us per step).
-    double JtJ[36], JtF[6], X[6], Xn[6], hh[6];
+    la::Mat<6, 6> JtJ;
+    la::Vec<6> hh;
+    double JtF[6], X[6], Xn[6];
 #pragma unroll
-    for (int i = 0; i < 36; i++) JtJ[i] = cJtJ[i];
+    for (int i = 0; i < 36; i++) JtJ.a[i] = cJtJ[i];
 #pragma unroll
     for (int i = 0; i < 6; i++) { JtF[i] = cJtF[i]; X[i] = cX[i]; Xn[i] = cXnew[i]; hh[i] = ch_h[i]; }
     double F = *cF, Fnew = *cFnew, F0 = *cF0, u = *cu, v = *cv;
@@ -2387,7 +2160,7 @@ __device__ __forceinline__ void lm_body(const LmArgs &a, const int seq, const in
                 for (int j = i + 1; j < 6; j++) Jn[j * 6 + i] = Jn[i * 6 + j];
             if (ops & LM_REDUCE_CUR) {
 #pragma unroll
-                for (int i = 0; i < 36; i++) JtJ[i] = Jn[i];
+                for (int i = 0; i < 36; i++) JtJ.a[i] = Jn[i];
 #pragma unroll
                 for (int i = 0; i < 6; i++) JtF[i] = Fn6[i];
             } else {
@@ -2404,9 +2177,9 @@ __device__ __forceinline__ void lm_body(const LmArgs &a, const int seq, const in
     const double tau = 1e-3;
     if (ops & LM_INIT) {
         F0 = F;
-        double mx = JtJ[0];
+        double mx = JtJ.a[0];
 #pragma unroll
-        for (int i = 1; i < 36; i++) mx = JtJ[i] > mx ? JtJ[i] : mx;  // TooN::max_element(JtJ).first
+        for (int i = 1; i < 36; i++) mx = JtJ.a[i] > mx ? JtJ.a[i] : mx;  // TooN::max_element(JtJ).first
         u = tau * mx;
     }
     if (ops & LM_RESET_V) v = 2;
@@ -2425,7 +2198,7 @@ __device__ __forceinline__ void lm_body(const LmArgs &a, const int seq, const in
 #pragma unroll
             for (int i = 0; i < 6; i++) { X[i] = Xn[i]; JtF[i] = cJtFnew[i]; }
 #pragma unroll
-            for (int i = 0; i < 36; i++) JtJ[i] = cJtJnew[i];
+            for (int i = 0; i < 36; i++) JtJ.a[i] = cJtJnew[i];
             const double g = 2 * gain - 1;
             const double m = 1 - (g * g * g);
             u *= (0.33 > m ? 0.33 : m);   // std::max(0.33, ...)
@@ -2455,11 +2228,10 @@ __device__ __forceinline__ void lm_body(const LmArgs &a, const int seq, const in
         const int t = res_new; res_new = res_cur; res_cur = t;       // std::swap
     }
     if (ops & (LM_SOLVE_SVD | LM_SOLVE_CHOL)) {
-        double ApI[36], nb[6];
+        la::Mat<6, 6> ApI = JtJ;
+        la::Vec<6> nb;
 #pragma unroll
-        for (int i = 0; i < 36; i++) ApI[i] = JtJ[i];
-#pragma unroll
-        for (int i = 0; i < 6; i++) { ApI[i * 7] = lm_rt(JtJ[i * 7] + 1.0 * u, a.f32); nb[i] = -JtF[i]; }
+        for (int i = 0; i < 6; i++) { ApI.a[i * 7] = lm_rt(JtJ.a[i * 7] + 1.0 * u, a.f32); nb[i] = -JtF[i]; }
         lm_solve6(ApI, nb, (ops & LM_SOLVE_SVD) != 0, hh, s_m, s_v);
 #pragma unroll
         for (int i = 0; i < 6; i++) { hh[i] = lm_rt(hh[i], a.f32); Xn[i] = lm_rt(X[i] + hh[i], a.f32); }
@@ -2468,17 +2240,15 @@ __device__ __forceinline__ void lm_body(const LmArgs &a, const int seq, const in
     if (ops & LM_PHASE_BC) sq->lm_phase = 1;
     // (the transform of the next evaluation is set up behind this block, on two lanes: tvr_setup2)
     if (ops & LM_FINISH) {
-        double L[36], Inv[36];
-        chol6_r(JtJ, L);
-        chol6_inverse_r(L, Inv);
+        const la::Mat<6, 6> Inv = la::Cholesky<6>(JtJ).inverse();
 #pragma unroll
         for (int i = 0; i < 3; i++) { sq->pub.V[i] = X[i]; sq->pub.W[i] = X[3 + i]; }
 #pragma unroll
         for (int i = 0; i < 3; i++)
 #pragma unroll
             for (int j = 0; j < 3; j++) {
-                sq->pub.P_V[i * 3 + j] = Inv[i * 6 + j];
-                sq->pub.P_W[i * 3 + j] = Inv[(i + 3) * 6 + j + 3];
+                sq->pub.P_V[i * 3 + j] = Inv(i, j);
+                sq->pub.P_W[i * 3 + j] = Inv(i + 3, j + 3);
             }
         if (eff_steps > 0) {
             double nh = 0, nx = 0;
@@ -2494,20 +2264,18 @@ __device__ __forceinline__ void lm_body(const LmArgs &a, const int seq, const in
         a.framecount[seq]++;
     }
     if (ops & LM_FINISH_KF) {
-        double L[36], Inv[36];
-        chol6_r(JtJ, L);
-        chol6_inverse_r(L, Inv);          // RRV = Cholesky<6>(JtJ).get_inverse()
+        const la::Mat<6, 6> Inv = la::Cholesky<6>(JtJ).inverse();   // RRV = Cholesky<6>(JtJ).get_inverse()
         edgehip_kf_result &o = a.kf_out[seq];
 #pragma unroll
         for (int i = 0; i < 6; i++) o.X[i] = X[i];
 #pragma unroll
-        for (int i = 0; i < 36; i++) o.RRV[i] = Inv[i];
+        for (int i = 0; i < 36; i++) o.RRV[i] = Inv.a[i];
         o.score_ratio = F / F0; o.F = F; o.F0 = F0;
         o.evals = sq->pub.minimizer_evals;
     }
     // registers -> state
 #pragma unroll
-    for (int i = 0; i < 36; i++) cJtJ[i] = JtJ[i];
+    for (int i = 0; i < 36; i++) cJtJ[i] = JtJ.a[i];
 #pragma unroll
     for (int i = 0; i < 6; i++) { cJtF[i] = JtF[i]; cX[i] = X[i]; cXnew[i] = Xn[i]; ch_h[i] = hh[i]; }
     *cF = F; *cFnew = Fnew; *cF0 = F0; *cu = u; *cv = v;
@@ -2748,41 +2516,6 @@ __global__ __launch_bounds__(256) void k_tv_resolve(double *__restrict__ resid, 
     if (is_carry(r[i])) r[i] = carry[(size_t)seq * nblk + blockIdx.x];
 }
 
-// util::Matrix3x3Inv (include/UtilLib/toon_util.h:32-41): adjugate / TooN::determinant, the latter by Gaussian
-// elimination with partial pivoting (TooN/determinant.h:91-146)
-__device__ inline double det3_ge(const double Ain[9]) {
-    double A[9];
-    for (int i = 0; i < 9; i++) A[i] = Ain[i];
-    double det = 1;
-    for (int i = 0; i < 3; i++) {
-        int argmax = i;
-        double maxval = fabs(A[i * 3 + i]);
-        for (int ii = i + 1; ii < 3; ii++) {
-            const double v = fabs(A[ii * 3 + i]);
-            if (v > maxval) { maxval = v; argmax = ii; }
-        }
-        const double pivot = A[argmax * 3 + i];
-        if (argmax != i) {
-            det *= -1;
-            for (int j = i; j < 3; j++) { const double t = A[i * 3 + j]; A[i * 3 + j] = A[argmax * 3 + j]; A[argmax * 3 + j] = t; }
-        }
-        det *= A[i * 3 + i];
-        if (det == 0) return 0;
-        for (int u = i + 1; u < 3; u++) {
-            const double factor = A[u * 3 + i] / pivot;
-            for (int j = i + 1; j < 3; j++) A[u * 3 + j] = A[u * 3 + j] - factor * A[i * 3 + j];
-        }
-    }
-    return det;
-}
-__device__ inline void mat3_inv(const double A[9], double B[9]) {
-    B[0] = A[8] * A[4] - A[7] * A[5]; B[1] = -(A[8] * A[1] - A[7] * A[2]); B[2] = A[5] * A[1] - A[4] * A[2];
-    B[3] = -(A[8] * A[3] - A[6] * A[5]); B[4] = A[8] * A[0] - A[6] * A[2]; B[5] = -(A[5] * A[0] - A[3] * A[2]);
-    B[6] = A[7] * A[3] - A[6] * A[4]; B[7] = -(A[7] * A[0] - A[6] * A[1]); B[8] = A[4] * A[0] - A[3] * A[1];
-    const double det = det3_ge(A);
-    for (int i = 0; i < 9; i++) B[i] = B[i] / det;
-}
-
 enum LmvOps : unsigned { LMV_BEGIN = 1, LMV_REDUCE_CUR = 2, LMV_REDUCE_NEW = 4, LMV_GAIN = 8, LMV_SOLVE = 16, LMV_FINISH = 32 };
 
 __global__ __launch_bounds__(64) void k_lmv_step(SeqDev *seqs, const double *__restrict__ partials, const double *__restrict__ block_last,
@@ -2808,11 +2541,12 @@ __global__ __launch_bounds__(64) void k_lmv_step(SeqDev *seqs, const double *__r
         }
         if (lane < nblk_used) bl = block_last[(size_t)seq * nblk + lane];
     }
-    double V[3], Vn[3], h[3], JtJ[9], JtF[3], JtJn[9], JtFn[3];
+    la::Mat<3, 3> JtJ;
+    double V[3], Vn[3], h[3], JtF[3], JtJn[9], JtFn[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) { V[i] = sq->mv_V[i]; Vn[i] = sq->mv_Vnew[i]; h[i] = sq->mv_h[i]; JtF[i] = sq->mv_JtF[i]; JtFn[i] = sq->mv_JtFnew[i]; }
 #pragma unroll
-    for (int i = 0; i < 9; i++) { JtJ[i] = sq->mv_JtJ[i]; JtJn[i] = sq->mv_JtJnew[i]; }
+    for (int i = 0; i < 9; i++) { JtJ.a[i] = sq->mv_JtJ[i]; JtJn[i] = sq->mv_JtJnew[i]; }
     double F = sq->mv_F, Fnew = sq->mv_Fnew, u = sq->mv_u, v = sq->mv_v;
     if (red) {
         if (lane < kTvNum) {
@@ -2843,16 +2577,16 @@ __global__ __launch_bounds__(64) void k_lmv_step(SeqDev *seqs, const double *__r
     const double tau = 1e-3;
     if (ops & LMV_BEGIN) v = 2;
     if (red) {
-        double *J = (ops & LMV_REDUCE_CUR) ? JtJ : JtJn;
+        double *J = (ops & LMV_REDUCE_CUR) ? JtJ.a : JtJn;
         double *Fv = (ops & LMV_REDUCE_CUR) ? JtF : JtFn;
         J[0] = s_sum[0]; J[4] = s_sum[1]; J[8] = s_sum[2];
         J[1] = J[3] = s_sum[3]; J[2] = J[6] = s_sum[4]; J[5] = J[7] = s_sum[5];
         Fv[0] = s_sum[6]; Fv[1] = s_sum[7]; Fv[2] = s_sum[8];
         if (ops & LMV_REDUCE_CUR) {
             F = s_sum[9];
-            double mx = JtJ[0];
+            double mx = JtJ.a[0];
 #pragma unroll
-            for (int i = 1; i < 9; i++) mx = JtJ[i] > mx ? JtJ[i] : mx;   // TooN::max_element(JtJ).first
+            for (int i = 1; i < 9; i++) mx = JtJ.a[i] > mx ? JtJ.a[i] : mx;   // TooN::max_element(JtJ).first
             u = tau * mx;
         } else {
             Fnew = s_sum[9];
@@ -2868,7 +2602,7 @@ __global__ __launch_bounds__(64) void k_lmv_step(SeqDev *seqs, const double *__r
 #pragma unroll
             for (int i = 0; i < 3; i++) { V[i] = Vn[i]; JtF[i] = JtFn[i]; }
 #pragma unroll
-            for (int i = 0; i < 9; i++) JtJ[i] = JtJn[i];
+            for (int i = 0; i < 9; i++) JtJ.a[i] = JtJn[i];
             const double g = 2 * gain - 1;
             const double m = 1 - (g * g * g);
             u *= (0.33 > m ? 0.33 : m);
@@ -2879,30 +2613,30 @@ __global__ __launch_bounds__(64) void k_lmv_step(SeqDev *seqs, const double *__r
         }
     }
     if (ops & LMV_SOLVE) {
-        double ApI[9], Inv[9];
+        la::Mat<3, 3> ApI;
 #pragma unroll
-        for (int i = 0; i < 9; i++) ApI[i] = JtJ[i] + ((i % 4 == 0) ? 1.0 * u : 0.0);
-        mat3_inv(ApI, Inv);
+        for (int i = 0; i < 9; i++) ApI.a[i] = JtJ.a[i] + ((i % 4 == 0) ? 1.0 * u : 0.0);
+        const la::Mat<3, 3> Inv = la::inv3(ApI);   // util::Matrix3x3Inv (toon_util.h:32-41)
 #pragma unroll
         for (int i = 0; i < 3; i++) {
             double d = 0;
 #pragma unroll
-            for (int k = 0; k < 3; k++) d += Inv[i * 3 + k] * (-JtF[k]);
+            for (int k = 0; k < 3; k++) d += Inv(i, k) * (-JtF[k]);
             h[i] = d;
             Vn[i] = V[i] + d;
         }
     }
-    double RVel[9];
-    if (ops & LMV_FINISH) mat3_inv(JtJ, RVel);
+    la::Mat<3, 3> RVel;
+    if (ops & LMV_FINISH) RVel = la::inv3(JtJ);
     // ---- stores ----
 #pragma unroll
     for (int i = 0; i < 3; i++) { sq->mv_V[i] = V[i]; sq->mv_Vnew[i] = Vn[i]; sq->mv_h[i] = h[i]; sq->mv_JtF[i] = JtF[i]; sq->mv_JtFnew[i] = JtFn[i]; }
 #pragma unroll
-    for (int i = 0; i < 9; i++) { sq->mv_JtJ[i] = JtJ[i]; sq->mv_JtJnew[i] = JtJn[i]; }
+    for (int i = 0; i < 9; i++) { sq->mv_JtJ[i] = JtJ.a[i]; sq->mv_JtJnew[i] = JtJn[i]; }
     sq->mv_F = F; sq->mv_Fnew = Fnew; sq->mv_u = u; sq->mv_v = v;
     if (ops & LMV_FINISH) {
 #pragma unroll
-        for (int i = 0; i < 9; i++) sq->mv_RVel[i] = RVel[i];
+        for (int i = 0; i < 9; i++) sq->mv_RVel[i] = RVel.a[i];
     }
 }
 

@@ -30,8 +30,10 @@
 
 #include "ctx.h"
 #include "wave_reduce.h"
+#include "rebvo/linalg.h"
 
 namespace edgehip {
+namespace la = rebvo::la;
 
 constexpr double kRhoMax = 20.0, kRhoMin = 1e-3, kRhoInit = 1.0;  // edge_finder.h:38-40
 
@@ -47,7 +49,6 @@ __global__ __launch_bounds__(256) void k_fwd_key(const KlSoA *kl_old, const int3
     if (f < 0 || f >= kn_new[seq]) return;
     atomicMax(&key[(size_t)seq * cap + f], ord_bits(kl_old[seq].rho[i]));
 }
-__device__ inline void so3_exp_c(const double w[3], double R[9]);
 __device__ inline void rot_from_state(SeqDev *sq, double *__restrict__ Rbuf_seq);
 __device__ inline void glue_after_tracking(SeqDev *sq);
 // tail_seqs != null (whole-frame driver, ImuMode 0): the first thread of a sequence's first block also does the two pieces of
@@ -114,7 +115,6 @@ __global__ __launch_bounds__(256) void k_fwd_apply(const KlSoA *kl_old, const Kl
 // rotate_keylines.  R given per sequence (row-major); when from_state != 0 each sequence uses
 // R0 = exp(W) from its state and stores the back-rotation R = R0^T (rebvo_second_t.cpp:360-361).
 // ---------------------------------------------------------------------------------------------------
-__device__ inline void so3_exp_c(const double w[3], double R[9]);
 
 // The turned values of a (slot, sequence) next to its own arrays (edgehip_ctx::rot_*; matching in one pass)
 struct RotOut {
@@ -141,13 +141,12 @@ __global__ __launch_bounds__(256) void k_rotate(const KlSoA *kls, const int32_t 
         if (blockIdx.x * 256 >= kns[seq] && blockIdx.x != 0) return;   // block-uniform
         if (threadIdx.x == 0) {
             SeqDev *sq = wa.seqs + seq;
-            double R0[9];
-            so3_exp_c(sq->pub.W, R0);
-            for (int q = 0; q < 9; q++) s_R[q] = R0[q];
+            const la::Mat<3, 3> R0 = la::so3_exp(la::Vec<3>{{sq->pub.W[0], sq->pub.W[1], sq->pub.W[2]}});
+            for (int q = 0; q < 9; q++) s_R[q] = R0.a[q];
             if (blockIdx.x == 0) {   // rot_from_state + glue_after_tracking
-                for (int q = 0; q < 9; q++) wa.Rbuf[(size_t)seq * 9 + q] = R0[q];
+                for (int q = 0; q < 9; q++) wa.Rbuf[(size_t)seq * 9 + q] = R0.a[q];
                 for (int a = 0; a < 3; a++)
-                    for (int b = 0; b < 3; b++) sq->pub.R[a * 3 + b] = R0[b * 3 + a];
+                    for (int b = 0; b < 3; b++) sq->pub.R[a * 3 + b] = R0(b, a);
                 glue_after_tracking(sq);
             }
         }
@@ -316,59 +315,12 @@ __global__ __launch_bounds__(256) void k_fwd_apply_rotate(const KlSoA *kl_old, c
 }
 #endif   // EDGEHIP_EXPERIMENTS
 
-// TooN SO3 exp / ln (so3.h:203-285, 288-334), device copies used by the frame glue
-__device__ inline void so3_exp_c(const double w[3], double R[9]) {
-    const double one_6th = 1.0 / 6.0, one_20th = 1.0 / 20.0;
-    const double theta_sq = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    const double theta = sqrt(theta_sq);
-    double A, B;
-    if (theta_sq < 1e-8) { A = 1.0 - one_6th * theta_sq; B = 0.5; }
-    else if (theta_sq < 1e-6) { B = 0.5 - 0.25 * one_6th * theta_sq; A = 1.0 - theta_sq * one_6th * (1.0 - one_20th * theta_sq); }
-    else { const double it = 1.0 / theta; A = sin(theta) * it; B = (1 - cos(theta)) * (it * it); }
-    const double wx2 = w[0] * w[0], wy2 = w[1] * w[1], wz2 = w[2] * w[2];
-    R[0] = 1.0 - B * (wy2 + wz2); R[4] = 1.0 - B * (wx2 + wz2); R[8] = 1.0 - B * (wx2 + wy2);
-    double a = A * w[2], b = B * (w[0] * w[1]);
-    R[1] = b - a; R[3] = b + a;
-    a = A * w[1]; b = B * (w[0] * w[2]);
-    R[2] = b + a; R[6] = b - a;
-    a = A * w[0]; b = B * (w[1] * w[2]);
-    R[5] = b - a; R[7] = b + a;
-}
-
-__device__ inline void so3_ln(const double M[9], double r[3]) {
-    const double cos_angle = (M[0] + M[4] + M[8] - 1.0) * 0.5;
-    r[0] = (M[7] - M[5]) / 2;
-    r[1] = (M[2] - M[6]) / 2;
-    r[2] = (M[3] - M[1]) / 2;
-    const double sin_angle_abs = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-    if (cos_angle > M_SQRT1_2) {
-        if (sin_angle_abs > 0) {
-            const double s = asin(sin_angle_abs) / sin_angle_abs;
-            r[0] *= s; r[1] *= s; r[2] *= s;
-        }
-    } else if (cos_angle > -M_SQRT1_2) {
-        const double s = acos(cos_angle) / sin_angle_abs;
-        r[0] *= s; r[1] *= s; r[2] *= s;
-    } else {
-        const double angle = M_PI - asin(sin_angle_abs);
-        const double d0 = M[0] - cos_angle, d1 = M[4] - cos_angle, d2 = M[8] - cos_angle;
-        double r2[3];
-        if (d0 * d0 > d1 * d1 && d0 * d0 > d2 * d2) { r2[0] = d0; r2[1] = (M[3] + M[1]) / 2; r2[2] = (M[2] + M[6]) / 2; }
-        else if (d1 * d1 > d2 * d2) { r2[0] = (M[3] + M[1]) / 2; r2[1] = d1; r2[2] = (M[7] + M[5]) / 2; }
-        else { r2[0] = (M[2] + M[6]) / 2; r2[1] = (M[7] + M[5]) / 2; r2[2] = d2; }
-        if (r2[0] * r[0] + r2[1] * r[1] + r2[2] * r[2] < 0) { r2[0] = -r2[0]; r2[1] = -r2[1]; r2[2] = -r2[2]; }
-        const double nn = sqrt(r2[0] * r2[0] + r2[1] * r2[1] + r2[2] * r2[2]);
-        for (int i = 0; i < 3; i++) r[i] = angle * (r2[i] / nn);
-    }
-}
-
 // R0 = exp(W); Rbuf[seq] = R0 (for k_rotate); state.R = R0^T * I^T ... i.e. R.T() = R0 * R.T() with R = I
 __device__ inline void rot_from_state(SeqDev *sq, double *__restrict__ Rbuf_seq) {
-    double R0[9];
-    so3_exp_c(sq->pub.W, R0);
-    for (int i = 0; i < 9; i++) Rbuf_seq[i] = R0[i];
+    const la::Mat<3, 3> R0 = la::so3_exp(la::Vec<3>{{sq->pub.W[0], sq->pub.W[1], sq->pub.W[2]}});   // TooN::SO3<>::exp
+    for (int i = 0; i < 9; i++) Rbuf_seq[i] = R0.a[i];
     for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) sq->pub.R[i * 3 + j] = R0[j * 3 + i];
+        for (int j = 0; j < 3; j++) sq->pub.R[i * 3 + j] = R0(j, i);
 }
 __global__ void k_rot_from_state(SeqDev *seqs, double *__restrict__ Rbuf, int nseq) {
     const int seq = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1000,9 +952,10 @@ __device__ inline void frame_end(SeqDev *sq, const int seq, const FrameEndArgs &
     // trip behind, and a load issued behind a store waits for it (the field-by-field version paid eight round trips).  Two
     // phases rather than one so that the live values fit the 128 registers of a 1024-thread block.
     {   // ---- pose integration: Pose = Pose*R; Pos += -Pose*V*K; P_V /= dt^2 ----
-        double Pose[9], R[9], V[3], Pos[3], P_V[9];
+        la::Mat<3, 3> Pose, R;
+        double V[3], Pos[3], P_V[9];
 #pragma unroll
-        for (int i = 0; i < 9; i++) { Pose[i] = p.Pose[i]; R[i] = p.R[i]; P_V[i] = p.P_V[i]; }
+        for (int i = 0; i < 9; i++) { Pose.a[i] = p.Pose[i]; R.a[i] = p.R[i]; P_V[i] = p.P_V[i]; }
 #pragma unroll
         for (int i = 0; i < 3; i++) { V[i] = p.V[i]; Pos[i] = p.Pos[i]; }
         const double K = p.K, dt = p.dt;
@@ -1014,32 +967,31 @@ __device__ inline void frame_end(SeqDev *sq, const int seq, const FrameEndArgs &
                 for (int j = 0; j < 3; j++) {
                     double d = 0;
 #pragma unroll
-                    for (int k = 0; k < 3; k++) d += Pose[i * 3 + k] * R[k * 3 + j];
+                    for (int k = 0; k < 3; k++) d += Pose.a[i * 3 + k] * R.a[k * 3 + j];
                     P2[i * 3 + j] = d;
                 }
 #pragma unroll
-            for (int i = 0; i < 9; i++) Pose[i] = P2[i];
+            for (int i = 0; i < 9; i++) Pose.a[i] = P2[i];
 #pragma unroll
             for (int i = 0; i < 3; i++) {
                 double d = 0;
 #pragma unroll
-                for (int k = 0; k < 3; k++) d += (-Pose[i * 3 + k]) * V[k];
+                for (int k = 0; k < 3; k++) d += (-Pose.a[i * 3 + k]) * V[k];
                 Pos[i] += d * K;
             }
 #pragma unroll
             for (int i = 0; i < 9; i++) P_V[i] /= dt * dt;
         }
-        double RotLie[3], PoseLie[3];
-        so3_ln(R, RotLie);
-        so3_ln(Pose, PoseLie);
+        // TooN::SO3<>::ln of the matrices as they are: no coerce
+        const la::Vec<3> RotLie = la::so3_ln_raw(R), PoseLie = la::so3_ln_raw(Pose);
         if (have_pair) {
 #pragma unroll
-            for (int i = 0; i < 9; i++) { p.Pose[i] = Pose[i]; p.P_V[i] = P_V[i]; }
+            for (int i = 0; i < 9; i++) { p.Pose[i] = Pose.a[i]; p.P_V[i] = P_V[i]; }
 #pragma unroll
             for (int i = 0; i < 3; i++) p.Pos[i] = Pos[i];
         }
 #pragma unroll
-        for (int i = 0; i < 9; i++) { o.Rot[i] = R[i]; o.Pose[i] = Pose[i]; }
+        for (int i = 0; i < 9; i++) { o.Rot[i] = R.a[i]; o.Pose[i] = Pose.a[i]; }
 #pragma unroll
         for (int i = 0; i < 3; i++) { o.RotLie[i] = RotLie[i]; o.PoseLie[i] = PoseLie[i]; o.Vel[i] = -V[i] * K / dt; o.Pos[i] = Pos[i]; }
         o.dt = dt;
@@ -1708,33 +1660,6 @@ int edgehip_get_stereo_matches(edgehip_ctx *c, int32_t *nmatch) {
     return 0;
 }
 
-// Host-side 6x6 symmetric eigen-decomposition (cyclic Jacobi), standing in for LAPACK dgesvd_ behind TooN::SVD<>
-static void jacobi_eig6_host(const double Ain[36], double V[36], double e[6]) {
-    double A[36];
-    for (int i = 0; i < 36; i++) { A[i] = Ain[i]; V[i] = 0; }
-    for (int i = 0; i < 6; i++) V[i * 7] = 1;
-    for (int sweep = 0; sweep < 60; sweep++) {
-        double off = 0, diag = 0;
-        for (int p = 0; p < 6; p++) {
-            diag += A[p * 7] * A[p * 7];
-            for (int q = p + 1; q < 6; q++) off += A[p * 6 + q] * A[p * 6 + q];
-        }
-        if (!(off > 1e-34 * diag) || !(off > 0)) break;
-        for (int p = 0; p < 5; p++)
-            for (int q = p + 1; q < 6; q++) {
-                const double apq = A[p * 6 + q];
-                if (apq == 0) continue;
-                const double theta = (A[q * 7] - A[p * 7]) / (2 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1));
-                const double cs = 1 / sqrt(t * t + 1), sn = t * cs;
-                for (int k = 0; k < 6; k++) { const double a = A[k * 6 + p], b = A[k * 6 + q]; A[k * 6 + p] = cs * a - sn * b; A[k * 6 + q] = sn * a + cs * b; }
-                for (int k = 0; k < 6; k++) { const double a = A[p * 6 + k], b = A[q * 6 + k]; A[p * 6 + k] = cs * a - sn * b; A[q * 6 + k] = sn * a + cs * b; }
-                for (int k = 0; k < 6; k++) { const double a = V[k * 6 + p], b = V[k * 6 + q]; V[k * 6 + p] = cs * a - sn * b; V[k * 6 + q] = sn * a + cs * b; }
-            }
-    }
-    for (int i = 0; i < 6; i++) e[i] = A[i * 7];
-}
-
 int edgehip_ext_rot_vel(edgehip_ctx *c, int slot, const double *vel, double loc_unc, double hub_reweight, double *X, double *Wx,
                         double *Rx, int32_t *ok) {
     EH_ENTER(c);
@@ -1758,44 +1683,31 @@ int edgehip_ext_rot_vel(edgehip_ctx *c, int slot, const double *vel, double loc_
         double sum[kNumSums] = {0};
         for (int b = 0; b < nblk; b++)
             for (int k = 0; k < kNumSums; k++) sum[k] += part[((size_t)s * c->nblk_tvr + b) * kNumSums + k];
-        double JtJ[36], JtF[6];
+        la::Mat<6, 6> JtJ;
+        la::Vec<6> JtF;
         int ns = 0;
         for (int a = 0; a < 6; a++)
-            for (int b = a; b < 6; b++) { JtJ[a * 6 + b] = sum[ns]; JtJ[b * 6 + a] = sum[ns]; ns++; }
+            for (int b = a; b < 6; b++) { JtJ(a, b) = sum[ns]; JtJ(b, a) = sum[ns]; ns++; }
         for (int a = 0; a < 6; a++) JtF[a] = sum[ns++];
         // X = SVD(JtJ).backsub(JtF), Rx = SVD(JtJ).get_pinv() with TooN's conditioning (SVD.h:176-207, 1e9)
         // A row at the pole 1 / rho + vel[2] == 0 (or with a NaN s_rho) leaves an infinity or a NaN in JtJ.  LAPACK's dgesvd_ answers
         // such a matrix with NaN singular values and vectors and TooN inverts those to NaN: X and Rx are NaN throughout.  (The Jacobi
         // sweeps would stop at once on it and, with an infinite diagonal entry, the cut would drop every eigenvalue: Rx = 0.)
         bool finite = true;
-        for (int i = 0; i < 36; i++) finite = finite && isfinite(JtJ[i]);
+        for (int i = 0; i < 36; i++) finite = finite && isfinite(JtJ.a[i]);
+        if (Wx) memcpy(Wx + (size_t)s * 36, JtJ.a, sizeof JtJ.a);
         if (!finite) {
             for (int i = 0; i < 6; i++) X[(size_t)s * 6 + i] = NAN;
             if (Rx)
                 for (int i = 0; i < 36; i++) Rx[(size_t)s * 36 + i] = NAN;
-            if (Wx) memcpy(Wx + (size_t)s * 36, JtJ, sizeof JtJ);
             if (ok) ok[s] = 0;
             continue;
         }
-        double V[36], e[6], inv[6], smax = 0;
-        jacobi_eig6_host(JtJ, V, e);
-        for (int i = 0; i < 6; i++) smax = fmax(smax, fabs(e[i]));
-        for (int i = 0; i < 6; i++) inv[i] = (fabs(e[i]) * 1e9 <= smax) ? 0.0 : 1.0 / e[i];
-        bool good = true;
-        for (int r = 0; r < 6; r++) {
-            double x = 0;
-            for (int cc = 0; cc < 6; cc++) {
-                double p = 0;
-                for (int i = 0; i < 6; i++) p += V[r * 6 + i] * inv[i] * V[cc * 6 + i];
-                if (Rx) Rx[(size_t)s * 36 + r * 6 + cc] = p;
-                if (p != p) good = false;
-                x += p * JtF[cc];
-            }
-            X[(size_t)s * 6 + r] = x;
-            if (x != x) good = false;
-        }
-        if (Wx) memcpy(Wx + (size_t)s * 36, JtJ, sizeof JtJ);
-        if (ok) ok[s] = good ? 1 : 0;
+        const la::Mat<6, 6> pinv = la::SymSVD<6>(JtJ).pinv();
+        const la::Vec<6> x = pinv * JtF;
+        for (int i = 0; i < 6; i++) X[(size_t)s * 6 + i] = x[i];
+        if (Rx) memcpy(Rx + (size_t)s * 36, pinv.a, sizeof pinv.a);
+        if (ok) ok[s] = (la::has_nan(pinv) || la::has_nan(x)) ? 0 : 1;
     }
     return 0;
 }

@@ -1,8 +1,10 @@
-// linalg.h — the small dense algebra the host-side IMU filters need (fixed sizes up to 11x11).
+// linalg.h — the small dense algebra of the project (fixed sizes up to 11x11), stated once for host and device: the IMU
+// filters, the key-frame constraint, the tracker's LM steps (6x6 and 3x3 solves, SO(3) maps of stage B), the frame glue
+// (exp / ln of stage C, ExtRotVel's pseudo-inverse) and the plane-fit constants all come here.
 //
 // The reference does this with TooN 2.2 (vendored as TooN-2.2.zip) and, behind TooN::SVD<>, LAPACK dgesvd_.
 // This header restates the TooN pieces with the same operation order (products are plain left-to-right sums
-// starting from 0, TooN/internal/operators.hh:198-208, 309-327), so that the filters agree with the reference to
+// starting from 0, TooN/internal/operators.hh:198-208, 309-327), so that its callers agree with the reference to
 // rounding; the only place that cannot be bit-identical is the SVD, which here is a cyclic Jacobi eigen-solve of
 // the (always symmetric) matrix instead of LAPACK.
 #ifndef REBVO_AMD_HOST_LINALG_H
@@ -170,20 +172,27 @@ REBVO_HD inline Mat<3, 3> inv3(const Mat<3, 3> &A) {
 }
 
 // ---- TooN::Cholesky<N>: L D L^T in place (TooN/Cholesky.h:88-125), backsub (:131-160), get_inverse (:165-200) -----
+// Written so that the device keeps everything in registers: every index is a constant once the loops are unrolled, and
+// TooN's return at a zero pivot (rank deficient: the rest of L stays as it was in A) is an `alive` flag instead of a way
+// out of the middle of an unrolled loop nest.
 template <int N>
 struct Cholesky {
     Mat<N, N> L;
     REBVO_HD explicit Cholesky(const Mat<N, N> &A) : L(A) {
+        bool alive = true;
+        REBVO_UNROLL
         for (int col = 0; col < N; col++) {
             double inv_diag = 1;
+            REBVO_UNROLL
             for (int row = col; row < N; row++) {
                 double val = L(row, col);
+                REBVO_UNROLL
                 for (int col2 = 0; col2 < col; col2++) val -= L(col2, col) * L(row, col2);
                 if (row == col) {
-                    L(row, col) = val;
-                    if (val == 0) return;   // rank deficient: TooN stops here too
+                    if (alive) L(row, col) = val;
+                    if (val == 0) alive = false;
                     inv_diag = 1 / val;
-                } else {
+                } else if (alive) {
                     L(col, row) = val;
                     L(row, col) = val * inv_diag;
                 }
@@ -192,14 +201,19 @@ struct Cholesky {
     }
     REBVO_HD Vec<N> backsub(const Vec<N> &v) const {
         Vec<N> y, r;
+        REBVO_UNROLL
         for (int i = 0; i < N; i++) {
             double val = v[i];
+            REBVO_UNROLL
             for (int j = 0; j < i; j++) val -= L(i, j) * y[j];
             y[i] = val;
         }
+        REBVO_UNROLL
         for (int i = 0; i < N; i++) y[i] /= L(i, i);
+        REBVO_UNROLL
         for (int i = N - 1; i >= 0; i--) {
             double val = y[i];
+            REBVO_UNROLL
             for (int j = i + 1; j < N; j++) val -= L(j, i) * r[j];
             r[i] = val;
         }
@@ -207,19 +221,29 @@ struct Cholesky {
     }
     REBVO_HD Mat<N, N> inverse() const {   // matrix backsub of the identity; the diagonal step multiplies by 1/d (:180-185)
         Mat<N, N> inv;
+        double invd[N];
+        REBVO_UNROLL
+        for (int i = 0; i < N; i++) invd[i] = 1 / L(i, i);
+        REBVO_UNROLL
         for (int c = 0; c < N; c++) {
             double y[N], r[N];
+            REBVO_UNROLL
             for (int i = 0; i < N; i++) {
                 double val = (i == c) ? 1.0 : 0.0;
+                REBVO_UNROLL
                 for (int j = 0; j < i; j++) val -= L(i, j) * y[j];
                 y[i] = val;
             }
-            for (int i = 0; i < N; i++) y[i] *= (1 / L(i, i));
+            REBVO_UNROLL
+            for (int i = 0; i < N; i++) y[i] *= invd[i];
+            REBVO_UNROLL
             for (int i = N - 1; i >= 0; i--) {
                 double val = y[i];
+                REBVO_UNROLL
                 for (int j = i + 1; j < N; j++) val -= L(j, i) * r[j];
                 r[i] = val;
             }
+            REBVO_UNROLL
             for (int i = 0; i < N; i++) inv(i, c) = r[i];
         }
         return inv;
@@ -312,8 +336,20 @@ struct SymSVD {
     }
     REBVO_HD Vec<N> backsub(const Vec<N> &b) const {
         Vec<N> y, x;
-        for (int i = 0; i < N; i++) { double d = 0; for (int k = 0; k < N; k++) d += V(k, i) * b[k]; y[i] = d * inv[i]; }
-        for (int k = 0; k < N; k++) { double d = 0; for (int i = 0; i < N; i++) d += V(k, i) * y[i]; x[k] = d; }
+        REBVO_UNROLL
+        for (int i = 0; i < N; i++) {
+            double d = 0;
+            REBVO_UNROLL
+            for (int k = 0; k < N; k++) d += V(k, i) * b[k];
+            y[i] = d * inv[i];
+        }
+        REBVO_UNROLL
+        for (int k = 0; k < N; k++) {
+            double d = 0;
+            REBVO_UNROLL
+            for (int i = 0; i < N; i++) d += V(k, i) * y[i];
+            x[k] = d;
+        }
         return x;
     }
     REBVO_HD Mat<N, N> pinv() const {
