@@ -581,6 +581,90 @@ int edgehip_upload_net_keylines(edgehip_ctx *ctx, int seq, const edgehip_net_key
  * fill or the record store is off. */
 int edgehip_depth_fill_net(edgehip_ctx *ctx, float p_off_x, float p_off_y);
 
+/* ---- the compressed edge map: KeyLine chains as fitted line segments -------------------------------------------------------
+ * edgemap_com_sender::compress_edgemap (src/CommLib/edgemap_com.cpp:162-326) with LineFitting::RobustFit3DLine<float>
+ * (src/UtilLib/linefitting.cpp:12-43, 111-204) under it, for every sequence of a slot: each chain of n_id links is walked from its head
+ * (p_id < 0), cut where the edge direction turns or the depth ratio jumps, a 3D line is fitted to each piece by weighted least squares,
+ * and the two end points of each piece leave as 5-byte compressed_kl records (include/CommLib/edgemap_com.h:45-51); a negative rho
+ * closes a polyline.  A few thousand bytes per frame instead of 168 (or 15) bytes per KeyLine.
+ *
+ * The walk is order dependent (heads in ascending index against a shared mask).  Walks touch only KeyLines reachable from their head, so
+ * walks in different weakly connected components of the n_id graph commute: the device labels the components, sorts the heads' keys
+ * (component, index) and runs one lane per component, its heads serially — exact on any link graph (merging chains, cycles, self-links).
+ * Records are numbered in head order over the whole list: a counting walk per head, a scan over the counts in index order, then the
+ * walk again with the fits.  The walk and the fit are the code of rebvo_amd/csrc/edgemap_fit.h, shared with the serial host restatement
+ * rebvo_compress_edgemap (rebvo_amd/host/include/rebvo/edgemap_com.h), whose records the device's equal byte for byte.
+ *
+ * The fit list (the reference's fit_list[max_line_len]) is stored nowhere: it always is the n_id path of f_inx KeyLines from the last
+ * cut, and the fit walks that path again (four passes of dependent loads, served by the L2).  One lane runs a whole component: a
+ * link graph that is one giant component (every chain merging into one) runs on a single lane of its sequence's workgroup.  No LDS or scratch is sized by
+ * max_line_len, so max_line_len has no upper limit.
+ * sin / cos of the fitted direction come from square roots and divisions instead of atan2, sin and cos (edgemap_fit.h): the same IEEE
+ * operations on host and device, but possibly another last bit of the double than glibc's before tx, ty and zfo are narrowed to float.
+ * Out of domain (the reference's integer conversions are undefined there): NaN or infinite rho / s_rho, s_rho <= 0. */
+#pragma pack(push, 1)
+typedef struct edgehip_compressed_kl {   /* rebvo::compressed_kl, byte for byte */
+    uint8_t x, y;           /* clamp_uchar(x * x_scaling), clamp_uchar(y * y_scaling) */
+    int16_t rho;            /* clamp_short(max(rho * (32767/20) / scale, (32767/20) * 1e-3)); negative: the polyline ends here */
+    uint8_t s_rho;          /* clamp_uchar(fit_sigma * (255/20)) */
+} edgehip_compressed_kl;
+#pragma pack(pop)
+#ifdef __cplusplus
+static_assert(sizeof(edgehip_compressed_kl) == 5, "compressed_kl is 5 bytes on the wire");
+#else
+_Static_assert(sizeof(edgehip_compressed_kl) == 5, "compressed_kl is 5 bytes on the wire");
+#endif
+typedef struct edgehip_edgemap_params {   /* compress_edgemap's arguments (edgemap_com.cpp:168) */
+    int32_t min_line_len;   /* >= 0 */
+    int32_t max_line_len;   /* >= 1 (the reference declares fit_list[max_line_len] and writes entry 0) */
+    int32_t match_n_t;      /* m_num below it: s_rho counts as 1e10 */
+    int32_t pad;
+    double max_angle;       /* radians; cos(max_angle) is taken once on the host */
+    double rho_rel_max;
+    double x_scaling, y_scaling;   /* 0 means the reference's COMPRESSED_X_SCALING 0.5 / COMPRESSED_Y_SCALING 1 (edgemap_com.h:42-43), whose
+                                      byte coordinates cover 510 x 255 pixels and clamp beyond; other values are this library's only
+                                      extension, for its own decoder */
+} edgehip_edgemap_params;
+#define EDGEHIP_EDGEMAP_BAD_LINK 1    /* status: a p_id / n_id outside [-1, kn) was read as -1 */
+#define EDGEHIP_EDGEMAP_OVERFLOW 2    /* status: more than cap_records records: count 0 (the reference's `return kl_num=0`) */
+#define EDGEHIP_EDGEMAP_STEP_GUARD 4  /* status: a walk ran into its bound of kn + 1 steps (no link graph does) */
+/* Allocates the store: nseq x cap_records records back to back (5 B each), a count and a status per sequence, and the scratch of the
+ * component pass (8 B per KeyLine and per record).  With min_line_len >= 1, cap_records = 2 * max_points cannot overflow.  0 frees
+ * everything.  A context that never calls this allocates and launches nothing; edgehip_process_frame never enqueues any of it.
+ * EDGEHIP_ERR_ARG for cap_records < 0; EDGEHIP_ERR_MEMORY when the allocation fails (the store is then off). */
+int edgehip_edgemap_enable(edgehip_ctx *ctx, int cap_records);
+/* compress_edgemap on the KeyLines of `slot` for every sequence, in-stream (no synchronisation); the slot is only read.  scale: host
+ * array [nseq] (the reference passes nav.K), or NULL for 1.  Camera: the context's principal point and zfm.  EDGEHIP_ERR_ARG for a
+ * slot out of range, min_line_len < 0, max_line_len < 1 or a negative scaling; EDGEHIP_ERR_STATE when the store is off. */
+int edgehip_edgemap_compress(edgehip_ctx *ctx, int slot, const edgehip_edgemap_params *params, const double *scale /* [nseq] or NULL */);
+/* The records of sequence `seq` (room for cap_records, *count are copied), their number and the status bits.  Any may be NULL.
+ * Synchronises. */
+int edgehip_download_edgemap(edgehip_ctx *ctx, int seq, edgehip_compressed_kl *records, int32_t *count, int32_t *status);
+/* The same for n sequences seqs[n]: records[j] (array or entries may be NULL), counts[n], status[n] (may be NULL).  Synchronises once
+ * for the counts and once for the records. */
+int edgehip_download_edgemap_batch(edgehip_ctx *ctx, int n, const int32_t *seqs, edgehip_compressed_kl *const *records, int32_t *counts,
+                                   int32_t *status);
+/* The stores of sequences [first, first+count) into DEVICE memory: records_dev[count][cap_records] records (5 B each, back to back) and
+ * counts_dev[count] int32 (either may be NULL), without a host bounce — like edgehip_net_keylines_device.  Complete on return. */
+int edgehip_edgemap_device(edgehip_ctx *ctx, int first, int count, void *records_dev, void *counts_dev);
+/* The records for output callbacks at full pipeline depth, through one more instance of the KeyLine export's staging ring (like
+ * edgehip_ros_export): edgehip_edgemap_compress on the OLD slot of the newest frame pair, in-stream, with scale[j] for sequence seqs[j]
+ * (1 for the others), then the lists of the n requested sequences, their counts and status words into a ring entry; nothing
+ * synchronises.  *ticket_out names the entry.  EDGEHIP_ERR_STATE before two frames or with the store off. */
+int edgehip_edgemap_export(edgehip_ctx *ctx, int n, const int32_t *seqs, const double *scale, const edgehip_edgemap_params *params, int *ticket_out);
+/* Enqueues the copies of a ticket on the ring's stream: up to max_records[j] records of list j to records_dst[j] (array or entries may
+ * be NULL) and pairs_dst[n][2] = (count, status) per list.  The count is known only on the device, so the caller bounds the copy: with
+ * min_line_len >= 1 a list has at most 2 * kn records.  The destinations are valid after edgehip_edgemap_export_wait. */
+int edgehip_edgemap_export_fetch(edgehip_ctx *ctx, int ticket, const int32_t *max_records, edgehip_compressed_kl *const *records_dst,
+                                 int32_t *pairs_dst);
+/* Blocks until the ticket's copies have landed (or, never fetched, its kernels have run) and frees the entry. */
+int edgehip_edgemap_export_wait(edgehip_ctx *ctx, int ticket);
+/* Measurement (tools/edgemap_compress_timing.py): device time of the last edgehip_edgemap_compress made under
+ * edgehip_profile_enable(ctx, 1), by HIP events: ms[0] component labelling, ms[1] the heads' keys and their sort (such a call runs
+ * the two as launches of their own, the labels crossing in HBM; otherwise they are one launch), ms[2] the walks (counting pass, scan,
+ * fitting pass), ms[3] the placement of the records.  EDGEHIP_ERR_STATE otherwise.  Waits for them. */
+int edgehip_edgemap_ms(edgehip_ctx *ctx, float ms[4]);
+
 /* ---- depth surface (what depth_filler's callers take from the grid) --------------------------------------------------------
  * From the grids of the last edgehip_depth_fill, for every sequence, in the camera frame and bit for bit as depth_filler computes them
  * (tests/depth_surface_port.py restates it), except the sign and payload of a NaN the arithmetic creates:

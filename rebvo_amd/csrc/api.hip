@@ -666,6 +666,7 @@ int edgehip_destroy(edgehip_ctx *c) {
     kf_track_free(c);
     jpeg_free(c);
     jpeg_decode_free(c);
+    edgemap_free(c);
     CtxAllocs *mine = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_allocs_mu);
@@ -689,6 +690,7 @@ int edgehip_destroy(edgehip_ctx *c) {
     if (c->aos_dev) { (void)hipFree(c->aos_dev); (void)hipHostFree(c->aos_host); (void)hipFree(c->aos_req_dev); (void)hipHostFree(c->aos_req_host); }
     c->kl_ring.close();
     c->ros_ring.close();
+    c->em_ring.close();
     c->jpeg_ring.close();
     if (c->stream_log) {
         (void)hipStreamSynchronize(c->stream_log); (void)hipStreamDestroy(c->stream_log); (void)hipEventDestroy(c->ev_log);

@@ -523,6 +523,7 @@ struct edgehip_ctx {
     // The lists of output callbacks without a host synchronisation, one staging ring (export_ring.h) per product:
     edgehip::ExportRing kl_ring;    // edgehip_export_keylines / _fetch / _wait: [n_cap][CAP] AoS KeyLine records per entry, int32 sequence ids per row
     edgehip::ExportRing jpeg_ring;  // edgehip_jpeg_export / _sizes / _fetch / _wait: [n_cap] regions | size records per entry, sequence ids | size records per row (jpeg_encode.hip)
+    edgehip::ExportRing em_ring;    // edgehip_edgemap_export / _fetch / _wait: [n_cap] record lists | (count, status) pairs per entry, scales | sequence ids per row (edgemap_compress.hip)
     edgehip::ExportRing ros_ring;   // edgehip_ros_export / _fetch / _wait: points | records per entry, k_prof | sequence ids per row (ros_edgemap.hip)
     edgehip_nav *nav_dev;  // [B] per-frame record
     edgehip_nav *nav_log;  // [nav_log_len][B] ring of per-frame records (optional)
@@ -592,6 +593,10 @@ struct edgehip_ctx {
     // edgehip_jpeg_decode_enable: compressed regions, descriptors, coefficient and sample planes of the JPEG decoder (jpeg_decode.hip); null when off
     struct JpegDec;
     JpegDec *jpegdec = nullptr;
+    // edgehip_edgemap_enable: every sequence's edge map as fitted line segments (5-byte compressed_kl records), their counts and status,
+    // and the scratch of the component pass (edgemap_compress.hip); null when off
+    struct EdgeMapStore;
+    EdgeMapStore *edgemap = nullptr;
 };
 
 namespace edgehip {
@@ -715,6 +720,7 @@ bool net_store(edgehip_ctx *c, const uint8_t **records, const edgehip_net_header
 void surface_views_free(edgehip_ctx *c);            // surface_integrate.hip
 void ros_free(edgehip_ctx *c);                      // ros_edgemap.hip: the stores, edgehip_destroy
 void jpeg_free(edgehip_ctx *c);                     // jpeg_encode.hip: edgehip_jpeg_enable(ctx, q, 0, NULL), edgehip_destroy
+void edgemap_free(edgehip_ctx *c);                  // edgemap_compress.hip: edgehip_edgemap_enable(ctx, 0), edgehip_destroy
 void jpeg_decode_free(edgehip_ctx *c);              // jpeg_decode.hip: edgehip_jpeg_decode_enable(ctx, n, 0), edgehip_destroy
 // api.hip, shared by the uploads on the upload stream: the slot reads its own storage again (RGB24 or 8-bit mono); the 8-bit storage
 // exists; stream_up waits for the last use of the slot's frame storage

@@ -26,6 +26,7 @@
 // decreases its distance and ends before that; a NaN p_m inside a link cycle (where the reference never returns) ends at the cap and sets
 // guard bit 1.
 #include "keyframe_track.h"
+#include "link_components.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -261,14 +262,6 @@ __global__ void k_kf_finish(KfArgs a, SeqDev *seqs) {
 }
 
 // ---- phase 2 ------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t kf_find(const uint32_t *lab, uint32_t i) {
-    while (1) {
-        const uint32_t l = __atomic_load_n(lab + i, __ATOMIC_RELAXED);
-        if (l == i) return i;
-        i = l;   // (a label only ever decreases and names a member of the same component: the chain ends at a root)
-    }
-}
-
 __global__ __launch_bounds__(kKfAugThreads) void k_kf_augment(KfArgs a) {
     extern __shared__ uint32_t kf_lds[];
     __shared__ int changed;
@@ -280,32 +273,8 @@ __global__ __launch_bounds__(kKfAugThreads) void k_kf_augment(KfArgs a) {
     int np2 = 1;
     while (np2 < kn) np2 <<= 1;
     uint32_t *buf = (a.use_lds && np2 <= kKfLdsKeys) ? kf_lds : a.keys + (size_t)seq * a.np2cap;
-    // 1. components of the own list's undirected link graph, labelled by their minimum index
-    for (int i = tid; i < kn; i += kKfAugThreads) buf[i] = (uint32_t)i;
-    __syncthreads();
-    while (1) {
-        if (tid == 0) changed = 0;
-        __syncthreads();
-        for (int i = tid; i < kn; i += kKfAugThreads) {
-            for (int side = 0; side < 2; side++) {
-                const int j = ldg(side ? v.own_n : v.own_p, i);
-                if (j < 0 || j >= kn || j == i) continue;
-                const uint32_t ra = kf_find(buf, (uint32_t)i), rb = kf_find(buf, (uint32_t)j);
-                if (ra != rb) {
-                    atomicMin(buf + max(ra, rb), min(ra, rb));
-                    changed = 1;
-                }
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < kn; i += kKfAugThreads) {
-            const uint32_t r = kf_find(buf, (uint32_t)i);
-            __atomic_store_n(buf + i, r, __ATOMIC_RELAXED);
-        }
-        const int again = changed;
-        __syncthreads();
-        if (!again) break;
-    }
+    // 1. components of the own list's undirected link graph, labelled by their minimum index (link_components.h)
+    lc_label_min<kKfAugThreads, 2>(buf, kn, &changed, [&](int i, int side) { return ldg(side ? v.own_n : v.own_p, i); });
     // 2. keys (label, index), sorted: every component's members in ascending index, components one after the other.  Only members that can
     // act get a key: a seed acts only where one of its links names a KeyLine that is unmatched at that moment, and during phase 2 a
     // KeyLine never goes from matched to unmatched (a failed correction writes -1 over a negative value) — so a member none of whose links
@@ -321,16 +290,7 @@ __global__ __launch_bounds__(kKfAugThreads) void k_kf_augment(KfArgs a) {
         buf[i] = key;
     }
     __syncthreads();
-    for (int size = 2; size <= np2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < (np2 >> 1); t += kKfAugThreads) {
-                const int lo = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), hi = lo | stride;
-                const uint32_t x = buf[lo], y = buf[hi];
-                const bool up = (lo & size) == 0;
-                if ((x > y) == up) { buf[lo] = y; buf[hi] = x; }
-            }
-            __syncthreads();
-        }
+    lc_sort<kKfAugThreads>(buf, np2);
     // 3. one lane per component, its members as seeds in ascending index
     int guard = 0;
     for (int k = tid; k < kn; k += kKfAugThreads) {

@@ -32,6 +32,9 @@ NET_KEYLINE_DTYPE = np.dtype({"names": ["qx", "qy", "rho", "s_rho", "n_kl", "m_n
                               "offsets": [0, 2, 4, 6, 8, 12, 13], "itemsize": 15})
 assert NET_KEYLINE_DTYPE.itemsize == 15
 NET_HEADER_DTYPE = np.dtype([("kline_num", "<i4"), ("km_num", "<i4"), ("k", "<f4")])   # edgehip_net_header
+# edgehip_compressed_kl = rebvo::compressed_kl (include/CommLib/edgemap_com.h:45-51), packed: 5 bytes
+COMPRESSED_KL_DTYPE = np.dtype({"names": ["x", "y", "rho", "s_rho"], "formats": ["u1", "u1", "<i2", "u1"], "offsets": [0, 1, 2, 4], "itemsize": 5})
+EDGEMAP_BAD_LINK, EDGEMAP_OVERFLOW, EDGEMAP_STEP_GUARD = 1, 2, 4   # status bits of edgehip_download_edgemap
 # edgehip_ros_point / edgehip_ros_keyline: what the ROS nodelet builds per KeyLine (ros/src/rebvo_ros/src/rebvo_nodelet.cpp:176-212):
 # one xyz point of the cloud, one rebvo/Keyline.msg record (its little-endian wire body, packed: 52 bytes)
 ROS_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
@@ -282,6 +285,13 @@ class KfDepth(C.Structure):
 
 KF_DEPTH_DTYPE = np.dtype(KfDepth)
 assert KF_DEPTH_DTYPE.itemsize == 32
+class EdgemapParams(C.Structure):
+    """edgehip_edgemap_params: compress_edgemap's arguments; x_scaling / y_scaling 0 mean the reference's 0.5 and 1."""
+    _fields_ = [("min_line_len", C.c_int32), ("max_line_len", C.c_int32), ("match_n_t", C.c_int32), ("pad", C.c_int32),
+                ("max_angle", C.c_double), ("rho_rel_max", C.c_double), ("x_scaling", C.c_double), ("y_scaling", C.c_double)]
+
+
+assert C.sizeof(EdgemapParams) == 48
 NAV_DTYPE = np.dtype(Nav)   # numpy view of edgehip_nav (same offsets as the ctypes struct)
 assert NAV_DTYPE.itemsize == C.sizeof(Nav)
 
@@ -310,6 +320,8 @@ EXPORTS = [
     "edgehip_download_surface_visibilities_batch", "edgehip_surface_ray_cross",
     "edgehip_net_enable", "edgehip_net_pack", "edgehip_download_net_keylines", "edgehip_download_net_keylines_batch",
     "edgehip_net_keylines_device", "edgehip_upload_net_keylines", "edgehip_depth_fill_net",
+    "edgehip_edgemap_enable", "edgehip_edgemap_compress", "edgehip_download_edgemap", "edgehip_download_edgemap_batch",
+    "edgehip_edgemap_device", "edgehip_edgemap_ms", "edgehip_edgemap_export", "edgehip_edgemap_export_fetch", "edgehip_edgemap_export_wait",
     "edgehip_ros_enable", "edgehip_ros_pack", "edgehip_download_ros_edgemap", "edgehip_download_ros_edgemaps_batch",
     "edgehip_ros_edgemap_device", "edgehip_ros_edgemap_from_device", "edgehip_ros_export", "edgehip_ros_export_fetch", "edgehip_ros_export_wait",
     "edgehip_match_one_pass",
@@ -941,6 +953,46 @@ class EdgeHip:
         if rec.dtype != NET_KEYLINE_DTYPE:
             rec = np.ascontiguousarray(rec, np.uint8).reshape(-1, 15)
         self._ck(self.lib.edgehip_upload_net_keylines(self.ctx, int(seq), C.c_void_p(rec.ctypes.data), len(rec)))
+
+    # ---- the compressed edge map: fitted line segments (compress_edgemap) ----
+    def edgemap_enable(self, cap_records):
+        """edgehip_edgemap_enable: room for cap_records 5-byte records per sequence; 0 (or None) frees the store."""
+        self._ck(self.lib.edgehip_edgemap_enable(self.ctx, int(cap_records or 0)))
+        self.edgemap_cap = int(cap_records or 0)
+
+    def edgemap_compress(self, slot, params, scale=None):
+        """edgehip_edgemap_compress: compress_edgemap on the KeyLines of `slot` for every sequence (in-stream).  params: an EdgemapParams;
+        scale: [nseq] or None for 1."""
+        sc = None if scale is None else np.ascontiguousarray(np.broadcast_to(np.asarray(scale, np.float64), (self.nseq,)))
+        self._ck(self.lib.edgehip_edgemap_compress(self.ctx, int(slot), C.byref(params), _dp(sc) if sc is not None else None))
+
+    def download_edgemap(self, seq):
+        """edgehip_download_edgemap -> (records: COMPRESSED_KL_DTYPE array of the sequence's count, status bits)."""
+        return self.download_edgemaps([seq])[0]
+
+    def download_edgemaps(self, seqs):
+        """edgehip_download_edgemap_batch -> [(records, status)] in the order of seqs."""
+        seqs = np.ascontiguousarray(seqs, dtype=np.int32)
+        n = len(seqs)
+        recs = [np.zeros(self.edgemap_cap, COMPRESSED_KL_DTYPE) for _ in range(n)]
+        counts, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        pr = (C.c_void_p * n)(*[r.ctypes.data for r in recs])
+        self._ck(self.lib.edgehip_download_edgemap_batch(self.ctx, n, seqs.ctypes.data_as(C.c_void_p), pr, C.c_void_p(counts.ctypes.data),
+                                                         C.c_void_p(status.ctypes.data)))
+        return [(recs[j][:counts[j]].copy(), int(status[j])) for j in range(n)]
+
+    def edgemap_into(self, records=None, counts=None, first=0):
+        """edgehip_edgemap_device: the stores of sequences [first, first + count) into torch tensors on the context's GPU: records uint8
+        (count, cap_records, 5), counts int32 (count,)."""
+        count = (records if records is not None else counts).shape[0]
+        self._ck(self.lib.edgehip_edgemap_device(self.ctx, int(first), int(count), C.c_void_p(records.data_ptr() if records is not None else None),
+                                                 C.c_void_p(counts.data_ptr() if counts is not None else None)))
+
+    def edgemap_ms(self):
+        """edgehip_edgemap_ms -> (labelling_ms, sort_ms, walks_ms, placement_ms) of the last edgemap_compress under profile_enable."""
+        ms = (C.c_float * 4)()
+        self._ck(self.lib.edgehip_edgemap_ms(self.ctx, ms))
+        return tuple(ms)
 
     def depth_fill_net(self, p_off=(0.0, 0.0)):
         """edgehip_depth_fill_net: the grids of every sequence from its stored wire records (in-stream)."""

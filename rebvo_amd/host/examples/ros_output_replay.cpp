@@ -3,6 +3,11 @@
 // PipeBuffer::point_cloud and PipeBuffer::edge_map_msg (&EdgeMapOutput PointCloud / KeylineMsg / KeyLineList in the GlobalConfig).
 //
 //   ros_output_replay <GlobalConfig> <frames.rgb24> <pool_frames> <objects> <frames_per_object> <t0> <dt> [--dump PREFIX] [--warmup W]
+//                     [--compressed PREFIX] [--single]
+// --single: the objects are not put into a batch group (each has its own context and tracking thread).
+// --compressed PREFIX (&EdgeMapOutput CompressedEdgeMap = 1): every callback prints its record count and bytes beside the KeyLine list's,
+// and appends to PREFIX.<i>.cem: int32 p_id, KNum(), count (-1: no compressed edge map), status, edgemap_id; float rho_scale; the KNum()
+// KeyLine records (168 bytes each); the count records (5 bytes each).
 //
 // Object i's frame k is pool frame tri(k + i), stamped t0 + k dt (surface_replay's scheme).  --dump PREFIX: every callback of object i
 // appends to PREFIX.<i>.ros, in binary: int32 p_id, KNum() of p.ef, cloud points (-1: no cloud), records (-1: no message); float64 K,
@@ -35,7 +40,21 @@ static int tri(long k, int n) {
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct Sink {
-    std::ofstream dump;
+    std::ofstream dump, cdump;
+    int index = 0;
+    void compressed(PipeBuffer &p) {
+        const CompressedEdgeMap *cm = p.edge_map_compressed;
+        const int kn = p.ef->KNum();
+        std::printf("compressed edge map: object %d frame %d: %d records, %d bytes (KeyLine list: %d, %zu bytes)\n", index, p.p_id, cm ? cm->count : -1,
+                    cm ? 5 * cm->count : 0, kn, (size_t)168 * kn);
+        const int32_t hdr[5] = {p.p_id, kn, cm ? cm->count : -1, cm ? cm->status : 0, cm ? (int32_t)cm->edgemap_id : 0};
+        const float scale = cm ? cm->rho_scale : 0.f;
+        cdump.write(reinterpret_cast<const char *>(hdr), sizeof hdr);
+        cdump.write(reinterpret_cast<const char *>(&scale), sizeof scale);
+        if (kn > 0) cdump.write(reinterpret_cast<const char *>(&(*p.ef)[0]), (std::streamsize)((size_t)168 * kn));
+        if (cm) cdump.write(reinterpret_cast<const char *>(cm->records.data()), (std::streamsize)(5 * (size_t)cm->count));
+        cdump.flush();
+    }
     std::atomic<int> calls{0};
     std::atomic<long> points{0};
     bool cb(PipeBuffer &p) {
@@ -43,6 +62,7 @@ struct Sink {
         const PointCloud *pc = p.point_cloud;
         const EdgeMapMsg *em = p.edge_map_msg;
         if (pc) points += pc->n;
+        if (cdump.is_open()) compressed(p);
         if (!dump.is_open()) return true;
         const int32_t hdr[4] = {p.p_id, p.ef->KNum(), pc ? pc->n : -1, em ? em->n : -1};
         dump.write(reinterpret_cast<const char *>(hdr), sizeof hdr);
@@ -63,10 +83,13 @@ int main(int argc, char **argv) {
     }
     const int pool_frames = std::atoi(argv[3]), N = std::atoi(argv[4]), K = std::atoi(argv[5]);
     const double t0 = std::atof(argv[6]), dt = std::atof(argv[7]);
-    std::string dump_prefix;
+    std::string dump_prefix, comp_prefix;
     int W = 0;
+    bool single = false;
     for (int a = 8; a < argc; a++) {
         if (!std::strcmp(argv[a], "--dump") && a + 1 < argc) dump_prefix = argv[++a];
+        else if (!std::strcmp(argv[a], "--compressed") && a + 1 < argc) comp_prefix = argv[++a];
+        else if (!std::strcmp(argv[a], "--single")) single = true;
         else if (!std::strcmp(argv[a], "--warmup") && a + 1 < argc) W = std::atoi(argv[++a]);
         else { std::cout << "unknown option " << argv[a] << "\n"; return 2; }
     }
@@ -74,8 +97,10 @@ int main(int argc, char **argv) {
     REBVO proto(argv[1]);
     if (!proto.isInitOk()) { std::cout << "config error\n"; return 3; }
     REBVOParameters prm = proto.getParams();
-    prm.GpuBatchGroup = "ros_output";
-    prm.GpuBatchSize = N;
+    if (!single) {
+        prm.GpuBatchGroup = "ros_output";
+        prm.GpuBatchSize = N;
+    }
     const Size2D sz = prm.ImageSize;
     const size_t fb = (size_t)sz.w * sz.h * 3;
     std::vector<uint8_t> pool(fb * pool_frames);
@@ -91,6 +116,8 @@ int main(int argc, char **argv) {
         sink.emplace_back(new Sink);
         if (!obj[i]->isInitOk()) { std::cout << "object " << i << ": bad parameters\n"; return 3; }
         if (!dump_prefix.empty()) sink[i]->dump.open(dump_prefix + "." + std::to_string(i) + ".ros", std::ios::binary);
+        sink[i]->index = i;
+        if (!comp_prefix.empty()) sink[i]->cdump.open(comp_prefix + "." + std::to_string(i) + ".cem", std::ios::binary);
         obj[i]->setOutputCallback(&Sink::cb, sink[i].get());
     }
     for (int i = 0; i < N; i++)

@@ -317,6 +317,17 @@ struct REBVOParameters {
     int EM_PointCloud = 0;
     int EM_KeylineMsg = 0;
     int EM_KeyLineList = 1;
+    //   CompressedEdgeMap = 1  PipeBuffer::edge_map_compressed: the edge map as fitted line segments, 5-byte compressed_kl records
+    //                          (edgemap_com_sender::compress_edgemap, src/CommLib/edgemap_com.cpp:162-326) with scale = the buffer's K,
+    //                          and compress_edgemap's arguments: MinLineLen (>= 1 here: a list then has at most 2 KNum() records),
+    //                          MaxLineLen, MaxAngle (radians), MatchNumThresh, RhoRelMax (the last two default as the reference's
+    //                          arguments do).  Members of a batch group must agree on all six; not delivered by ImuMode 1 / 2 groups.
+    int EM_Compressed = 0;
+    int EM_MinLineLen = 3;
+    int EM_MaxLineLen = 50;
+    double EM_MaxAngle = 0.3;
+    int EM_MatchNumThresh = 0;
+    double EM_RhoRelMax = 1e10;
 };
 
 // Filter state SecondThread keeps in the IMU branch (reference include/rebvo/rebvo.h:239-290, same member names).
@@ -388,6 +399,16 @@ struct EdgeMapMsg {
     std::vector<uint8_t> records;
 };
 
+// (mirror only) &EdgeMapOutput CompressedEdgeMap: count records of 5 bytes (compressed_kl: x, y, rho as a short, s_rho), the scale they were
+// made with (rho_scale = the buffer's K, what edgemap_com keeps beside them) and the object's running edge-map number (1 for the first).
+struct CompressedEdgeMap {
+    int count = 0;
+    int status = 0;                 // EDGEHIP_EDGEMAP_* bits (0: fine)
+    float rho_scale = 1;
+    uint16_t edgemap_id = 0;
+    std::vector<uint8_t> records;   // 5 * count bytes
+};
+
 struct PipeBuffer {
     sspace *ss = nullptr;
     global_tracker *gt = nullptr;
@@ -417,6 +438,7 @@ struct PipeBuffer {
     const PointCloud *point_cloud = nullptr;       // (mirror only) &EdgeMapOutput PointCloud = 1: from exactly this buffer's edge map and K, valid
                                                    // during the output callback; null when off or the delivery carries no edge map
     const EdgeMapMsg *edge_map_msg = nullptr;      // (mirror only) &EdgeMapOutput KeylineMsg = 1: likewise
+    const CompressedEdgeMap *edge_map_compressed = nullptr;   // (mirror only) &EdgeMapOutput CompressedEdgeMap = 1: likewise
     const uint8_t *jpeg = nullptr;                 // (mirror only) VideoSave or VideoNetEnabled, objects on the group engine: this frame as the
     size_t jpeg_size = 0;                          // encoder hands it on (EncoderType 1: the JPEG, 0: the raw RGB24), valid during the output callback.
                                                    // With UseUndistort the JPEG is of the undistorted frame (the reference's imgc); the raw
@@ -475,6 +497,8 @@ class REBVO {
     std::map<const PipeBuffer *, std::unique_ptr<DepthImage>> df_images;
     std::map<const PipeBuffer *, std::unique_ptr<PointCloud>> em_clouds;   // &EdgeMapOutput: the products behind each ring buffer's pointers
     std::map<const PipeBuffer *, std::unique_ptr<EdgeMapMsg>> em_msgs;
+    std::map<const PipeBuffer *, std::unique_ptr<CompressedEdgeMap>> em_compressed;
+    uint16_t em_compressed_id = 0;   // edge maps compressed so far (edgemap_com::edge_map_id)
     std::map<const PipeBuffer *, std::vector<uint8_t>> video_frames;   // VideoSave / VideoNetEnabled: the encoded frame behind each ring buffer's jpeg
     std::vector<char> video_save;   // VideoSave: VideoSaveBuffersize bytes, video_save_at of them filled; written to VideoSaveFile when the object stops
     size_t video_save_at = 0;

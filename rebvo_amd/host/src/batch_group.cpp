@@ -168,11 +168,16 @@ public:
     // ... and, with &EdgeMapOutput, the nodelet's cloud / records of the same edge maps (edgehip_ros_export, a ring of its own): `aos` / `ros` say
     // which of the two tickets the step holds (KeyLineList = 0: no AoS lists)
     struct Export { long step = -1; int ticket = 0; std::vector<int32_t> seats; bool fetched = false; bool aos = false;
-                    bool ros = false, ros_fetched = false; int ros_ticket = 0; };
+                    bool ros = false, ros_fetched = false; int ros_ticket = 0;
+                    // ... and, with CompressedEdgeMap, the fitted segments (edgehip_edgemap_export, a third ring): emc_pairs[j] = (count, status)
+                    bool emc = false, emc_fetched = false; int emc_ticket = 0; std::vector<int32_t> emc_pairs, emc_max;
+                    std::vector<CompressedEdgeMap *> emc_dst; };
     Export exp_of[4];              // [step & 3]
     // &DepthFiller (the same for every member): after a step, the grids of the edge maps its callbacks get (edgehip_depth_fill on the old slot)
     int em_what = 0;               // &EdgeMapOutput PointCloud | KeylineMsg as EDGEHIP_ROS_* bits (the same for every member)
     bool em_list = true;           // &EdgeMapOutput KeyLineList
+    bool em_comp = false;          // &EdgeMapOutput CompressedEdgeMap, and compress_edgemap's arguments (the same for every member)
+    edgehip_edgemap_params emp{};
     bool dfill = false;
     edgehip_depth_fill_params dfp{};
     edgehip_depth_surface_params dsp{};   // Surface / DenseImage (both 0: off)
@@ -228,6 +233,8 @@ public:
 
     void threadMain();
     int exportFetch(Export &ex, const std::vector<int32_t> &kn, const std::vector<edgehip_keyline *> &dst);
+    int emcFetch(Export &ex, const std::vector<PipeBuffer *> &buf);   // likewise for the compressed edge maps
+    void emcLanded(Export &ex);                                       // behind the ticket's wait: counts, status, scale, number
     int rosFetch(Export &ex, const std::vector<PipeBuffer *> &buf);   // buf[j]: the PipeBuffer seat ex.seats[j]'s products land behind (null: none)
     void dropExports();
     bool gather(bool block, bool &any_running, bool &any_leaving);
@@ -280,6 +287,8 @@ bool REBVO::groupAttach() {
     if (dfill) { dsp.surface = params.DF_Surface != 0; dsp.image_mode = params.DF_DenseImage; }
     const int em_what = (params.EM_PointCloud ? EDGEHIP_ROS_POINTS : 0) | (params.EM_KeylineMsg ? EDGEHIP_ROS_KEYLINES : 0);
     const bool em_list = params.EM_KeyLineList != 0;
+    const bool em_comp = params.EM_Compressed != 0;
+    const edgehip_edgemap_params emp = detail::edgemap_params(params);
     // TrackKeyFrames: ImuMode 0 and no stereo pair (the device's IMU branch refuses it; other objects ignore the key, as before)
     const bool kf_track = params.TrackKeyFrames && !imu_mode && !stereo;
     const double kf_pct = kf_track ? params.KFSavePercent : 0;
@@ -290,6 +299,10 @@ bool REBVO::groupAttach() {
     };
     if (imu_mode && em_what)
         return fail("REBVO(hip): &GPU BatchGroup with ImuMode 1 / 2 does not deliver &EdgeMapOutput PointCloud / KeylineMsg (a frame's K is known only after the next frame has been enqueued)");
+    if (imu_mode && em_comp)
+        return fail("REBVO(hip): &GPU BatchGroup with ImuMode 1 / 2 does not deliver &EdgeMapOutput CompressedEdgeMap (a frame's K is known only after the next frame has been enqueued)");
+    if (em_comp && (params.EM_MinLineLen < 1 || params.EM_MaxLineLen < 1))
+        return fail("REBVO(hip): &EdgeMapOutput CompressedEdgeMap needs MinLineLen >= 1 and MaxLineLen >= 1");
     if (want < 1) return fail("REBVO(hip): &GPU BatchGroup needs BatchSize >= 1 (the number of objects that share the context)");
     if (params.GpuTrackerPrecision == 32 && (imu_mode || stereo))   // (edgehip_imu_enable / edgehip_set_stereo_rig refuse it too)
         return fail("REBVO(hip): &GPU TrackerPrecision=32 is Minimizer_RV<float>, the tracker of ImuMode 0 without a stereo pair");
@@ -334,6 +347,9 @@ bool REBVO::groupAttach() {
         if (rc == 0) rc = edgehip_set_nav_log(g->hip, BatchGroup::kNavLog);
         g->em_what = em_what;
         g->em_list = em_list;
+        g->em_comp = em_comp;
+        g->emp = emp;
+        if (rc == 0 && em_comp) rc = edgehip_edgemap_enable(g->hip, 2 * params.MaxPoints + 2);
         g->dfill = dfill;
         g->dfp = dfp;
         g->dsp = dsp;
@@ -387,6 +403,8 @@ bool REBVO::groupAttach() {
             return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same TrackKeyFrames and KFSavePercent");
         if (g->em_what != em_what || g->em_list != em_list)
             return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same &EdgeMapOutput PointCloud, KeylineMsg and KeyLineList");
+        if (g->em_comp != em_comp || (em_comp && std::memcmp(&g->emp, &emp, sizeof emp) != 0))
+            return fail("REBVO(hip): BatchGroup '" + g->name + "': every member needs the same &EdgeMapOutput CompressedEdgeMap, MinLineLen, MaxLineLen, MaxAngle, MatchNumThresh and RhoRelMax");
     }
     std::unique_lock<std::mutex> lk(g->mut);
     if (g->started && g->attached >= g->cap) {
@@ -1059,7 +1077,7 @@ int REBVO::BatchGroup::launch(long step, const std::vector<double> &ts) {
             ex.seats.push_back(i);
         }
         if (!ex.seats.empty()) {
-            ex.aos = ex.ros = false;
+            ex.aos = ex.ros = ex.emc = false;
             if (em_list) {
                 rc = edgehip_export_keylines(hip, (int)ex.seats.size(), ex.seats.data(), &ex.ticket);
                 if (rc != 0) return rc;
@@ -1071,6 +1089,13 @@ int REBVO::BatchGroup::launch(long step, const std::vector<double> &ts) {
                 if (rc != 0) return rc;
                 ex.ros = true;
                 ex.ros_fetched = false;
+            }
+            if (em_comp) {   // the same edge maps as fitted segments, scale = the K their buffers carry (1, as above)
+                const std::vector<double> ks(ex.seats.size(), 1.0);
+                rc = edgehip_edgemap_export(hip, (int)ex.seats.size(), ex.seats.data(), ks.data(), &emp, &ex.emc_ticket);
+                if (rc != 0) return rc;
+                ex.emc = true;
+                ex.emc_fetched = false;
             }
             ex.step = step;
             ex.fetched = false;
@@ -1251,6 +1276,43 @@ int REBVO::BatchGroup::rosFetch(Export &ex, const std::vector<PipeBuffer *> &buf
     return rc;
 }
 
+int REBVO::BatchGroup::emcFetch(Export &ex, const std::vector<PipeBuffer *> &buf) {
+    const size_t n = ex.seats.size();
+    ex.emc_pairs.assign(2 * n, 0);
+    ex.emc_max.assign(n, 0);
+    ex.emc_dst.assign(n, nullptr);
+    std::vector<edgehip_compressed_kl *> rd(n, nullptr);
+    for (size_t j = 0; j < n; j++) {
+        PipeBuffer *b = buf[j];
+        if (!b) continue;
+        REBVO *cf = seats[ex.seats[j]].cf;
+        std::unique_ptr<CompressedEdgeMap> &cm = cf->em_compressed[b];
+        if (!cm) cm.reset(new CompressedEdgeMap);
+        ex.emc_max[j] = 2 * b->ef->kn + 2;   // MinLineLen >= 1: no list is longer (the count itself is known only on the device)
+        cm->count = 0;
+        cm->records.resize(5 * (size_t)ex.emc_max[j]);
+        rd[j] = reinterpret_cast<edgehip_compressed_kl *>(cm->records.data());
+        ex.emc_dst[j] = cm.get();
+    }
+    const int rc = edgehip_edgemap_export_fetch(hip, ex.emc_ticket, ex.emc_max.data(), rd.data(), ex.emc_pairs.data());
+    if (rc == 0) ex.emc_fetched = true;
+    return rc;
+}
+
+void REBVO::BatchGroup::emcLanded(Export &ex) {
+    for (size_t j = 0; j < ex.emc_dst.size(); j++) {
+        CompressedEdgeMap *cm = ex.emc_dst[j];
+        if (!cm) continue;
+        int count = ex.emc_pairs[2 * j], status = ex.emc_pairs[2 * j + 1];
+        if (count < 0 || count > ex.emc_max[j]) { count = 0; status |= EDGEHIP_EDGEMAP_OVERFLOW; }
+        cm->count = count;
+        cm->status = status;
+        cm->rho_scale = 1.0f;
+        cm->edgemap_id = ++seats[ex.seats[j]].cf->em_compressed_id;
+        cm->records.resize(5 * (size_t)count);
+    }
+}
+
 // Every export still outstanding is waited for (or dropped): before KeyLine arrays are unpinned, a copy must not be on its way into them.
 void REBVO::BatchGroup::dropExports() {
     videoFlush();
@@ -1258,6 +1320,7 @@ void REBVO::BatchGroup::dropExports() {
         if (ex.step >= 0) {
             if (ex.aos) (void)edgehip_export_wait(hip, ex.ticket);
             if (ex.ros) (void)edgehip_ros_export_wait(hip, ex.ros_ticket);
+            if (ex.emc) (void)edgehip_edgemap_export_wait(hip, ex.emc_ticket);
             ex.step = -1;
         }
 }
@@ -1336,6 +1399,7 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
             ob.depth_image = nullptr;
             ob.point_cloud = nullptr;
             ob.edge_map_msg = nullptr;
+            ob.edge_map_compressed = nullptr;
             const auto vf = cf->video_frames.find(&ob);
             ob.jpeg = cf->wantsVideo() && vf != cf->video_frames.end() && !vf->second.empty() ? vf->second.data() : nullptr;
             ob.jpeg_size = ob.jpeg ? vf->second.size() : 0;
@@ -1422,8 +1486,19 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
             for (size_t j = 0; j < ex.seats.size(); j++) buf[j] = deliver[ex.seats[j]];
             rc = rosFetch(ex, buf);
         }
+        if (ex.emc && !ex.emc_fetched && rc == 0) {
+            std::vector<PipeBuffer *> buf(ex.seats.size(), nullptr);
+            for (size_t j = 0; j < ex.seats.size(); j++) buf[j] = deliver[ex.seats[j]];
+            rc = emcFetch(ex, buf);
+        }
         if (ex.aos) { const int rw = edgehip_export_wait(hip, ex.ticket); if (rc == 0) rc = rw; }
         if (ex.ros) { const int rw = edgehip_ros_export_wait(hip, ex.ros_ticket); if (rc == 0) rc = rw; }
+        if (ex.emc) {
+            const bool landed = ex.emc_fetched;
+            const int rw = edgehip_edgemap_export_wait(hip, ex.emc_ticket);
+            if (rc == 0) rc = rw;
+            if (rc == 0 && landed) emcLanded(ex);
+        }
         ex.step = -1;
         if (rc != 0) {
             std::cout << "\nREBVO: KeyLine export failed: " << edgehip_last_error() << "\n";
@@ -1435,6 +1510,7 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
                 REBVO *cf = seats[seat].cf;
                 if (ex.ros && (em_what & EDGEHIP_ROS_POINTS) && cf->em_clouds.count(ob)) ob->point_cloud = cf->em_clouds[ob].get();
                 if (ex.ros && (em_what & EDGEHIP_ROS_KEYLINES) && cf->em_msgs.count(ob)) ob->edge_map_msg = cf->em_msgs[ob].get();
+                if (ex.emc && ex.emc_fetched && cf->em_compressed.count(ob)) ob->edge_map_compressed = cf->em_compressed[ob].get();
                 if (!em_list) ob->ef->kn = 0;   // &EdgeMapOutput KeyLineList = 0: the callback's list stays empty
             }
         }
@@ -1454,6 +1530,11 @@ int REBVO::BatchGroup::complete(long step, int slot, std::vector<edgehip_nav> &n
             std::vector<PipeBuffer *> buf(nx.seats.size(), nullptr);
             for (size_t j = 0; j < nx.seats.size(); j++) buf[j] = mine[nx.seats[j]];
             rc = rosFetch(nx, buf);
+        }
+        if (rc == 0 && nx.step == step + 1 && nx.emc && !nx.emc_fetched) {
+            std::vector<PipeBuffer *> buf(nx.seats.size(), nullptr);
+            for (size_t j = 0; j < nx.seats.size(); j++) buf[j] = mine[nx.seats[j]];
+            rc = emcFetch(nx, buf);
         }
     }
     for (int i = 0; i < cap; i++) {   // (PipeBuffer::img, the grey image a callback may look at, is formed by the member's output thread)
@@ -1744,6 +1825,46 @@ extern "C" int rebvo_group_edgemap_selftest(const char *config_file) {
     if (!e.Init()) return 6;   // the same keys: the group starts
     a.CleanUp();
     e.CleanUp();
+    return 0;
+}
+
+// Likewise for &EdgeMapOutput CompressedEdgeMap and compress_edgemap's five arguments: 0 = every disagreeing member was refused
+extern "C" int rebvo_group_compressed_edgemap_selftest(const char *config_file) {
+    using namespace rebvo;
+    REBVO proto(config_file);
+    if (!proto.isInitOk()) return 1;
+    REBVOParameters p = proto.getParams();
+    p.CameraType = 3; p.ImuMode = 0; p.StereoAvaiable = false;
+    p.GpuBatchGroup = "emc_selftest";
+    p.GpuBatchSize = 2;
+    p.EM_Compressed = 1;
+    REBVO a(p);
+    if (!a.Init()) return 2;
+    for (int k = 0; k < 6; k++) {
+        REBVOParameters q = p;
+        if (k == 0) q.EM_Compressed = 0;
+        if (k == 1) q.EM_MinLineLen++;
+        if (k == 2) q.EM_MaxLineLen++;
+        if (k == 3) q.EM_MaxAngle += 0.01;
+        if (k == 4) q.EM_MatchNumThresh++;
+        if (k == 5) q.EM_RhoRelMax = 2.0;
+        REBVO b(q);
+        if (b.Init() || b.lastError().find("CompressedEdgeMap") == std::string::npos) return 3 + k;
+    }
+    REBVO e(p);
+    if (!e.Init()) return 9;   // the same keys: the group starts
+    a.CleanUp();
+    e.CleanUp();
+    return 0;
+}
+
+// The six keys of the compressed edge map as the GlobalConfig parser reads them (CPU test hook, needs no device)
+extern "C" int rebvo_compressed_edgemap_config(const char *config_file, int *ints, double *reals) {
+    rebvo::REBVO proto(config_file);
+    if (!proto.isInitOk()) return 1;
+    const rebvo::REBVOParameters p = proto.getParams();
+    ints[0] = p.EM_Compressed; ints[1] = p.EM_MinLineLen; ints[2] = p.EM_MaxLineLen; ints[3] = p.EM_MatchNumThresh;
+    reals[0] = p.EM_MaxAngle; reals[1] = p.EM_RhoRelMax;
     return 0;
 }
 

@@ -331,6 +331,12 @@ REBVO::REBVO(const char *configFile)
     config.get("EdgeMapOutput", "PointCloud", p.EM_PointCloud, false);    // optional section, ours
     config.get("EdgeMapOutput", "KeylineMsg", p.EM_KeylineMsg, false);
     config.get("EdgeMapOutput", "KeyLineList", p.EM_KeyLineList, false);
+    config.get("EdgeMapOutput", "CompressedEdgeMap", p.EM_Compressed, false);
+    config.get("EdgeMapOutput", "MinLineLen", p.EM_MinLineLen, false);
+    config.get("EdgeMapOutput", "MaxLineLen", p.EM_MaxLineLen, false);
+    config.get("EdgeMapOutput", "MaxAngle", p.EM_MaxAngle, false);
+    config.get("EdgeMapOutput", "MatchNumThresh", p.EM_MatchNumThresh, false);
+    config.get("EdgeMapOutput", "RhoRelMax", p.EM_RhoRelMax, false);
     construct();
 }
 
@@ -491,6 +497,16 @@ bool REBVO::Init() {
     }
     if (rc == 0 && (params.EM_PointCloud || params.EM_KeylineMsg))   // &EdgeMapOutput: the stores the output callback's products are packed into
         rc = edgehip_ros_enable(hip, (params.EM_PointCloud ? EDGEHIP_ROS_POINTS : 0) | (params.EM_KeylineMsg ? EDGEHIP_ROS_KEYLINES : 0));
+    if (rc == 0 && params.EM_Compressed) {
+        if (params.EM_MinLineLen < 1 || params.EM_MaxLineLen < 1) {
+            last_error = "REBVO(hip): &EdgeMapOutput CompressedEdgeMap needs MinLineLen >= 1 and MaxLineLen >= 1";
+            std::cout << last_error << "\n";
+            if (hip) edgehip_destroy(hip);
+            hip = nullptr;
+            return false;
+        }
+        rc = edgehip_edgemap_enable(hip, 2 * params.MaxPoints + 2);
+    }
     if (rc != 0) {   // no CPU fallback: fail loudly
         last_error = std::string("REBVO(hip): edgehip_create failed: ") + edgehip_last_error();
         std::cout << last_error << "\n";
@@ -688,6 +704,27 @@ void REBVO::TrackThread(REBVO *cf) {
                 } else {
                     if (em_what & EDGEHIP_ROS_POINTS) { pc->n = kn_em; pc->xyz.resize(3 * (size_t)kn_em); old_buf->point_cloud = pc.get(); }
                     if (em_what & EDGEHIP_ROS_KEYLINES) { em->n = kn_em; em->records.resize(sizeof(edgehip_ros_keyline) * (size_t)kn_em); old_buf->edge_map_msg = em.get(); }
+                }
+                rc = 0;
+            }
+            old_buf->edge_map_compressed = nullptr;
+            if (want && cf->params.EM_Compressed && rc == 0) {   // &EdgeMapOutput CompressedEdgeMap: the same edge map as fitted segments
+                const int so = (slot + 2) % 3;
+                const double K = old_buf->K;
+                const edgehip_edgemap_params ep = detail::edgemap_params(cf->params);
+                std::unique_ptr<CompressedEdgeMap> &cm = cf->em_compressed[old_buf];
+                if (!cm) cm.reset(new CompressedEdgeMap);
+                cm->records.resize(5 * (size_t)(2 * cf->params.MaxPoints + 2));
+                int32_t n_em = 0, st_em = 0;
+                rc = edgehip_edgemap_compress(cf->hip, so, &ep, &K);
+                if (rc == 0) rc = edgehip_download_edgemap(cf->hip, 0, reinterpret_cast<edgehip_compressed_kl *>(cm->records.data()), &n_em, &st_em);
+                if (rc != 0) {
+                    std::cout << "\nREBVO: edgehip_edgemap_compress failed: " << edgehip_last_error() << "\n";
+                    failed = true;
+                } else {
+                    cm->count = n_em; cm->status = st_em; cm->rho_scale = (float)K; cm->edgemap_id = ++cf->em_compressed_id;
+                    cm->records.resize(5 * (size_t)n_em);
+                    old_buf->edge_map_compressed = cm.get();
                 }
                 rc = 0;
             }
