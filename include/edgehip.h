@@ -665,6 +665,65 @@ int edgehip_edgemap_export_wait(edgehip_ctx *ctx, int ticket);
  * fitting pass), ms[3] the placement of the records.  EDGEHIP_ERR_STATE otherwise.  Waits for them. */
 int edgehip_edgemap_ms(edgehip_ctx *ctx, float ms[4]);
 
+/* ---- the compressed edge map, received: segments, visibility, depth grid ---------------------------------------------------
+ * edgemap_com_decoder (include/CommLib/edgemap_com.h:226-252, src/CommLib/edgemap_com.cpp:42-160, 431-528) over the record store of
+ * edgehip_edgemap_enable, for every sequence in one launch per step.  The store takes records from edgehip_edgemap_compress (which
+ * also leaves the scale it used as the store's rho_scale, the double narrowed to float as the reference's rho_scale=scale narrows it)
+ * or from edgehip_upload_edgemap.  The rules are rebvo_amd/csrc/edgemap_seg.h, shared with the serial host restatements decode,
+ * hide_visible and fill_depth_map of rebvo/edgemap_com.h, whose results the device's equal bit for bit.
+ *
+ * Departures from the reference, all of them:
+ *   - getPair's cursor walk is evaluated as a rule local to a record (it starts a segment iff it is not the last record, its rho is
+ *     not 0, and it is not a negative record behind a positive one); every list gives the segments the walk gives, in its order.
+ *   - A list with more than cap_segments segments is cut in order and flagged (the reference's bound is KEYLINE_MAX), and the fill
+ *     folds the decoded segments: fillDepthMap reads the records through getPair again, which differs only for a list that was cut.
+ *   - fillDepthMap updates a cell once per step of a segment, in segment and then step order; here those (segment, step) items are
+ *     numbered by a scan and brought to their cells by the stable ordered scatter of the fill, so a cell sees the same updates in the
+ *     same order.  A sequence with more than cap_items items folds none (the reference has no bound) and is flagged.
+ *   - use_visibility != 0 skips hidden segments in the fill.  The reference's fillDepthMap ignores visi_mask; 0 is its behaviour.
+ *   - x_scaling / y_scaling other than the reference's 0.5 and 1 (edgehip_edgemap_params).
+ *   - (int) of a step's position converts as an x86-64 build converts it; a direction of infinite length (only with scalings that
+ *     overflow a float) is a sequence over cap_items rather than an endless loop.
+ * Not built: GetLowerKL (it sums a histogram it never zeroes) and dfillerHideVisible (per-cell visibility of two fillers). */
+#define EDGEHIP_EDGEMAP_SEGMENT_OVERFLOW 1   /* decoder status: more than cap_segments segments; the first cap_segments are kept */
+#define EDGEHIP_EDGEMAP_ITEM_OVERFLOW 2      /* decoder status: the last edgehip_depth_fill_segments met more than cap_items steps: none folded */
+/* `count` records (and the rho_scale of their header) become sequence seq's stored edge map: the counterpart of
+ * edgehip_upload_net_keylines.  EDGEHIP_ERR_ARG for count outside [0, cap_records] or a rho_scale that is not finite, is <= 0 or is so
+ * small (below about 5e-36) that getPair's divisor (32767 / 20) / rho_scale is no finite float; EDGEHIP_ERR_STATE when the store is
+ * off.  Synchronises.
+ * Domain of everything below: a store whose rho_scale passes this test.  Then the local decode rule equals getPair's walk on every
+ * list, every decoded rho is a positive finite float and every s_rho at least 1e-3, and no record list puts a NaN into the grid.
+ * edgehip_edgemap_compress / _export store the scale they are given unchecked (they always accepted any double): a NaN, infinite, zero,
+ * negative or vanishing scale there is out of domain for the decoder (NaN or +-0 rho; no gate compares true on a NaN, so it folds). */
+int edgehip_upload_edgemap(edgehip_ctx *ctx, int seq, const edgehip_compressed_kl *records, int32_t count, float rho_scale);
+/* Allocates the decoder: per sequence cap_segments segments (8 floats and a visibility byte; 44 B more for the fill's direction and
+ * offset) and cap_items (segment, step) items (8 B each).  cap_segments 0 frees it.  A context that never calls this allocates and
+ * launches nothing; edgehip_process_frame never enqueues any of it.  EDGEHIP_ERR_ARG outside [0, 2^24]. */
+int edgehip_edgemap_decode_enable(edgehip_ctx *ctx, int cap_segments, int cap_items);
+/* edgemap_com_decoder::Decode on every sequence's stored records, in-stream: segments in record order, every visibility flag 1.
+ * x_scaling / y_scaling as the sender's (0: the reference's 0.5 and 1).  EDGEHIP_ERR_STATE when the decoder or the store is off. */
+int edgehip_edgemap_decode(edgehip_ctx *ctx, double x_scaling, double y_scaling);
+/* Segments (k0, k1: x, y, rho, s_rho; room for cap_segments x 8 floats), visibility flags (cap_segments bytes), their number and the
+ * decoder's status bits of sequence `seq`.  Any may be NULL.  Synchronises. */
+int edgehip_download_edgemap_segments(edgehip_ctx *ctx, int seq, float *segments, uint8_t *flags, int32_t *count, int32_t *status);
+int edgehip_download_edgemap_segments_batch(edgehip_ctx *ctx, int n, const int32_t *seqs, float *const *segments, uint8_t *const *flags,
+                                            int32_t *counts, int32_t *status);
+/* edgemap_com_decoder::HideVisible on every sequence whose rows are not NULL: dpose[seq] (9 doubles, row-major) and dpos[seq] (3) are
+ * GetDPose() / GetDPos() after UpdatePos (rebvo::edgemap::update_pos computes them on the host), k_em[seq] the stored map's K and
+ * k_new[seq] the new view's.  A segment whose k0 or k1, moved by TransformPos, lands inside the context's frame with rho > 0 loses
+ * its flag; a flag that is 0 stays 0.  s_num_out[nseq] (may be NULL): segments that were visible and stay visible, -1 for a sequence
+ * left alone.  Synchronises. */
+int edgehip_edgemap_hide_visible(edgehip_ctx *ctx, const double *const *dpose, const double *const *dpos, const float *k_em, const float *k_new,
+                                 int32_t *s_num_out);
+/* The third source of the depth fill: ResetData, edgemap_com_decoder::fillDepthMap(df, cam, v_thresh, a_thresh) on the decoded
+ * segments, InitCoarseFine, Integrate(iter_num), in-stream, with the block size, iter_num and bound_mode of edgehip_depth_fill_enable
+ * and the context's camera.  Writes the same grids as edgehip_depth_fill and shares no other state with it.  use_visibility: see the
+ * departures above.  EDGEHIP_ERR_STATE when the fill or the decoder is off or nothing was decoded. */
+int edgehip_depth_fill_segments(edgehip_ctx *ctx, double v_thresh, double a_thresh_deg, int use_visibility);
+/* Measurement (tools/edgemap_decode_timing.py): device time of the last decode, hide, item and fill launch made under
+ * edgehip_profile_enable(ctx, 1), by HIP events; -1 for a stage not run so.  Waits for them. */
+int edgehip_edgemap_decode_ms(edgehip_ctx *ctx, float ms[4]);
+
 /* ---- depth surface (what depth_filler's callers take from the grid) --------------------------------------------------------
  * From the grids of the last edgehip_depth_fill, for every sequence, in the camera frame and bit for bit as depth_filler computes them
  * (tests/depth_surface_port.py restates it), except the sign and payload of a NaN the arithmetic creates:

@@ -666,6 +666,7 @@ int edgehip_destroy(edgehip_ctx *c) {
     kf_track_free(c);
     jpeg_free(c);
     jpeg_decode_free(c);
+    edgemap_decode_free(c);
     edgemap_free(c);
     CtxAllocs *mine = nullptr;
     {

@@ -597,6 +597,10 @@ struct edgehip_ctx {
     // and the scratch of the component pass (edgemap_compress.hip); null when off
     struct EdgeMapStore;
     EdgeMapStore *edgemap = nullptr;
+    // edgehip_edgemap_decode_enable: every sequence's decoded segments, visibility flags and the (segment, step) items of the segment
+    // source of the depth fill (edgemap_decode.hip); null when off
+    struct EdgeMapDecode;
+    EdgeMapDecode *emdec = nullptr;
 };
 
 namespace edgehip {
@@ -721,6 +725,23 @@ void surface_views_free(edgehip_ctx *c);            // surface_integrate.hip
 void ros_free(edgehip_ctx *c);                      // ros_edgemap.hip: the stores, edgehip_destroy
 void jpeg_free(edgehip_ctx *c);                     // jpeg_encode.hip: edgehip_jpeg_enable(ctx, q, 0, NULL), edgehip_destroy
 void edgemap_free(edgehip_ctx *c);                  // edgemap_compress.hip: edgehip_edgemap_enable(ctx, 0), edgehip_destroy
+// edgemap_compress.hip: the record store ([nseq][cap_records] records of 5 B, back to back), counts and rho_scale; false when off
+bool edgemap_store(edgehip_ctx *c, const uint8_t **records, const int32_t **counts, const float **rho_scale, int *cap_records);
+void edgemap_decode_free(edgehip_ctx *c);           // edgemap_decode.hip: edgehip_edgemap_decode_enable(ctx, 0, 0), edgehip_destroy
+// edgemap_decode.hip: what the segment source of k_depth_fill reads.  An item is a (segment, step) pair, numbered by segment, then by
+// step: segment s owns the items [seg_off[s], seg_off[s + 1]).
+struct SegSource {
+    const float *seg;          // [nseq][cap_segments][8] k0, k1: x, y, rho, s_rho
+    const int32_t *seg_num;    // [nseq]
+    const int32_t *seg_off;    // [nseq][cap_segments + 1]
+    const double *seg_dir;     // [nseq][cap_segments][4] tx, ty, r1, kl_I_rho of a segment with steps
+    const int32_t *items;      // [nseq] items to fold: 0 when they exceed cap_items
+    int32_t *cell, *ids;       // [nseq][cap_items] binning scratch
+    int cap_segments, cap_items;
+};
+void edgemap_decode_mark(edgehip_ctx *c, int stage, bool end);   // HIP events of stage 0 .. 3 (decode, hide, items, fill) under edgehip_profile_enable
+// gates and step counts of every decoded segment (k_em_items), enqueued; EDGEHIP_ERR_STATE when nothing was decoded yet
+int edgemap_items_enqueue(edgehip_ctx *c, double v_thresh, double a_thresh_deg, int use_visibility, SegSource *out);
 void jpeg_decode_free(edgehip_ctx *c);              // jpeg_decode.hip: edgehip_jpeg_decode_enable(ctx, n, 0), edgehip_destroy
 // api.hip, shared by the uploads on the upload stream: the slot reads its own storage again (RGB24 or 8-bit mono); the 8-bit storage
 // exists; stream_up waits for the last use of the slot's frame storage

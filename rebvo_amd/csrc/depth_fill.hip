@@ -13,16 +13,23 @@
 //                t-3 .. t-1, the four below / to the right by sweep k-1 at steps t-3 .. t-1 and by sweep k not before t+1: exactly the
 //                values the raster loop reads, in one buffer.  (With a skew of 3 sweep k+1 would reach (x-1, y-1) at the step at which
 //                sweep k updates (x, y).)  No two cells of one step are neighbours.
-// Two sources feed stages 1 and 2 (template parameter NET of k_depth_fill; stages 3 and 4 are the same code for both):
+// Three sources feed stages 1 and 2 (template parameter SRC of k_depth_fill; stages 3 and 4 are the same code for all; below NET is
+// SRC == kDfNet and SEG is SRC == kDfSeg):
 //   NET = false  the slot's SoA KeyLines with FillEdgeData(edge_tracker&, ...)'s gates (:113-163): the key-frame path's overload;
 //   NET = true   a sequence's 15-byte wire records (net_keyline.hip) with FillEdgeData(net_keyline*, kn, p_off, ...)'s (:59-104): the
 //                visualizer's overload (visualizer.cpp:436-439).  rho and s_rho come back from their 1 / NET_RHO_SCALING quanta, the cell from
 //                (qx + p_off.x) / bl_size.w in float; there is no p_id / n_id / rho <= 0 gate and no rho0.
+//   SEG          a sequence's decoded line segments (edgemap_decode.hip) as edgemap_com_decoder::fillDepthMap rasterises them
+//                (src/CommLib/edgemap_com.cpp:475-528): what is binned and folded is a (segment, step) item, numbered by segment and
+//                then by step — the order the reference's two nested loops update a cell in.  k_em_items has applied the gates and
+//                scanned the step counts; an item finds its segment by bisection of those offsets, its cell by getImgPoint's unsigned
+//                division and clamp (edgemap_seg.h), and folds rho = r1 * step + k0.rho with the segment's 1 / s_rho^2.
 // The grid lives in LDS while it fits in 64 KB (rho, s_rho: 16 B per cell, fixed: 1 B — 3 600 cells at 10-px blocks of 752x480)
 // and in the context's output arrays in HBM otherwise (14 400 cells at 5-px blocks); the code is the same on both.
 // fp64 throughout; '/' and sqrt are the compiler's correctly rounded operations, the cell index uses its correctly rounded float
 // division, and -ffp-contract=off keeps every product and sum separately rounded as in the reference.
 #include "ctx.h"
+#include "edgemap_seg.h"
 
 #include <cmath>
 #include <cstring>
@@ -58,7 +65,20 @@ struct DfArgs {
     const edgehip_net_header *net_hdr;   // [nseq]
     int net_kl_size;
     float p_off_x, p_off_y;
+    // SEG: the decoded segments and their items instead of kls / kns (cap: cap_items; cell / ids: the decoder's)
+    SegSource seg;
 };
+enum { kDfKeyLines = 0, kDfNet = 1, kDfSeg = 2 };
+
+// the segment that owns item i: the last s with off[s] <= i (a segment without steps has off[s] == off[s + 1] and is passed over)
+__device__ __forceinline__ int df_seg_of(const int32_t *off, int nseg, int i) {
+    int lo = 0, hi = nseg;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 
 constexpr double kNetRhoScale = 10000.0;   // NET_RHO_SCALING, include/CommLib/net_keypoint.h:32
 // the fields FillEdgeData reads of wire record i (net_keyline: qx, qy, rho, s_rho at bytes 0 .. 7, m_num at byte 12), byte loads: a record is aligned to nothing
@@ -86,14 +106,20 @@ __device__ __forceinline__ bool df_inboundary(int x, int y, int gw, int gh, int 
     return false;
 }
 
-template <bool NET>
+template <int SRC>
 __global__ __launch_bounds__(kDfThreads) void k_depth_fill(DfArgs a, DfLevels lv) {
+    constexpr bool NET = SRC == kDfNet, SEG = SRC == kDfSeg;
     extern __shared__ __align__(16) unsigned char df_lds[];
     __shared__ int32_t part[kDfThreads];
     const int seq = blockIdx.x, tid = threadIdx.x;
     const int gw = a.gw, gh = a.gh, G = gw * gh;
-    const KlSoA &k = a.kls[NET ? 0 : seq];   // (NET: not read)
-    const int kn = NET ? max(0, min(min(a.net_hdr[seq].kline_num, a.net_kl_size), a.cap)) : min(a.kns[seq], a.cap);
+    const KlSoA &k = a.kls[NET || SEG ? 0 : seq];   // (NET, SEG: not read)
+    const int kn = SEG ? max(0, min(a.seg.items[seq], a.cap))
+                       : NET ? max(0, min(min(a.net_hdr[seq].kline_num, a.net_kl_size), a.cap)) : min(a.kns[seq], a.cap);
+    const int nseg = SEG ? max(0, min(a.seg.seg_num[seq], a.seg.cap_segments)) : 0;
+    const float *sseg = SEG ? a.seg.seg + (size_t)seq * a.seg.cap_segments * 8 : nullptr;
+    const int32_t *soff = SEG ? a.seg.seg_off + (size_t)seq * (a.seg.cap_segments + 1) : nullptr;
+    const double *sdir = SEG ? a.seg.seg_dir + (size_t)seq * a.seg.cap_segments * 4 : nullptr;
     const uint8_t *nrec = NET ? a.net_rec + (size_t)seq * a.net_kl_size * 15 : nullptr;
     int32_t *cell = a.cell + (size_t)seq * a.cap;
     int32_t *cnt = a.cnt + (size_t)seq * G;
@@ -112,6 +138,16 @@ __global__ __launch_bounds__(kDfThreads) void k_depth_fill(DfArgs a, DfLevels lv
     // 1. cells (FillEdgeData's tests, in its order) and counts
     for (int i = tid; i < kn; i += kDfThreads) {
         int c = -1;
+        if constexpr (SEG) {   // (kn > 0 only with nseg > 0; every item has a cell: getImgPoint clamps into the grid)
+            const int sg = df_seg_of(soff, nseg, i);
+            rebvo::edgemap::SegSteps st;
+            st.q0x = sseg[8 * sg]; st.q0y = sseg[8 * sg + 1];
+            st.tx = sdir[4 * sg]; st.ty = sdir[4 * sg + 1];
+            c = rebvo::edgemap::seg_step_cell(st, i - soff[sg], a.bw, a.bh, gw, gh);
+            cell[i] = c;
+            atomicAdd(&cnt[c], 1);
+            continue;
+        }
         if constexpr (NET) {
             const DfNetRec n = df_net_rec(nrec, i);
             const double r = n.rho / kNetRhoScale, s = n.s_rho / kNetRhoScale;
@@ -187,7 +223,13 @@ __global__ __launch_bounds__(kDfThreads) void k_depth_fill(DfArgs a, DfLevels lv
         for (int j = b0; j < b1; j++) {
             const int i = ids[j];
             double r, kl_I;
-            if constexpr (NET) {
+            if constexpr (SEG) {
+                const int sg = df_seg_of(soff, nseg, i);
+                rebvo::edgemap::SegSteps st;
+                st.r1 = sdir[4 * sg + 2]; st.rho0 = sseg[8 * sg + 2];
+                r = rebvo::edgemap::seg_step_rho(st, i - soff[sg]);
+                kl_I = sdir[4 * sg + 3];   // (the update below is the one loop all three sources share; seg_fold is the host's copy of it)
+            } else if constexpr (NET) {
                 const DfNetRec n = df_net_rec(nrec, i);
                 r = n.rho / kNetRhoScale;
                 double s = n.s_rho / kNetRhoScale;
@@ -443,7 +485,8 @@ int edgehip_depth_fill(edgehip_ctx *c, int slot) {
     a.ntiles = d->ntiles; a.v_thresh = d->p.thresh_rel_rho; a.use_lds = d->use_lds;
     const size_t lds = d->use_lds ? (size_t)d->gw * d->gh * 17 : 0;
     a.net_rec = nullptr; a.net_hdr = nullptr; a.net_kl_size = 0; a.p_off_x = a.p_off_y = 0.f;
-    hipLaunchKernelGGL(k_depth_fill<false>, dim3(c->plan.nseq), dim3(kDfThreads), lds, c->stream, a, d->lv);
+    a.seg = SegSource{};
+    hipLaunchKernelGGL(k_depth_fill<kDfKeyLines>, dim3(c->plan.nseq), dim3(kDfThreads), lds, c->stream, a, d->lv);
     EH_LAUNCH_CHECK();
     d->filled = true;
     return slot_read_done(c, slot);   // a later stage A that detects into this slot waits for the fill's reads
@@ -478,8 +521,34 @@ int edgehip_depth_fill_net(edgehip_ctx *c, float p_off_x, float p_off_y) {
     a.iter_num = d->p.iter_num; a.bound_mode = d->p.bound_mode; a.discard = d->p.discard != 0; a.m_num_t = d->p.thresh_match_num;
     a.ntiles = d->ntiles; a.v_thresh = d->p.thresh_rel_rho; a.use_lds = d->use_lds;
     a.p_off_x = p_off_x; a.p_off_y = p_off_y;
+    a.seg = SegSource{};
     const size_t lds = d->use_lds ? (size_t)d->gw * d->gh * 17 : 0;
-    hipLaunchKernelGGL(k_depth_fill<true>, dim3(c->plan.nseq), dim3(kDfThreads), lds, c->stream, a, d->lv);
+    hipLaunchKernelGGL(k_depth_fill<kDfNet>, dim3(c->plan.nseq), dim3(kDfThreads), lds, c->stream, a, d->lv);
+    EH_LAUNCH_CHECK();
+    d->filled = true;
+    return 0;
+}
+
+int edgehip_depth_fill_segments(edgehip_ctx *c, double v_thresh, double a_thresh_deg, int use_visibility) {
+    EH_ENTER(c);
+    auto *d = c->dfill;
+    if (!d) { set_error("depth_fill_segments: depth fill is not enabled (edgehip_depth_fill_enable)"); return EDGEHIP_ERR_STATE; }
+    if (std::isnan(v_thresh) || std::isnan(a_thresh_deg)) { set_error("depth_fill_segments: NaN threshold"); return EDGEHIP_ERR_ARG; }
+    DfArgs a;
+    if (int e = edgemap_items_enqueue(c, v_thresh, a_thresh_deg, use_visibility, &a.seg)) return e;
+    a.kls = kldev(c, 0); a.kns = c->kn_slot;   // not read
+    a.cell = a.seg.cell; a.ids = a.seg.ids; a.cap = a.seg.cap_items;
+    a.cnt = d->cnt; a.off = d->off;
+    a.tile_r = d->tile_r; a.tile_s = d->tile_s; a.tile_n = d->tile_n;
+    a.rho = d->rho; a.s_rho = d->s_rho; a.fixed = d->fixed;
+    a.gw = d->gw; a.gh = d->gh; a.bw = d->p.block_w; a.bh = d->p.block_h;
+    a.iter_num = d->p.iter_num; a.bound_mode = d->p.bound_mode; a.discard = 0; a.m_num_t = 0;
+    a.ntiles = d->ntiles; a.v_thresh = v_thresh; a.use_lds = d->use_lds;
+    a.net_rec = nullptr; a.net_hdr = nullptr; a.net_kl_size = 0; a.p_off_x = a.p_off_y = 0.f;
+    const size_t lds = d->use_lds ? (size_t)d->gw * d->gh * 17 : 0;
+    edgemap_decode_mark(c, 3, false);
+    hipLaunchKernelGGL(k_depth_fill<kDfSeg>, dim3(c->plan.nseq), dim3(kDfThreads), lds, c->stream, a, d->lv);
+    edgemap_decode_mark(c, 3, true);
     EH_LAUNCH_CHECK();
     d->filled = true;
     return 0;

@@ -19,6 +19,7 @@
 // nothing is written unless that total is at most cap_records (else count 0 and EDGEHIP_EDGEMAP_OVERFLOW).
 #include "ctx.h"
 #include "edgemap_fit.h"
+#include "edgemap_seg.h"
 #include "link_components.h"
 #include "pack_flush.h"
 
@@ -49,6 +50,7 @@ struct EmArgs {
     unsigned long long *tmp;  // [nseq][cap_records] records at their final numbers, unpacked
     uint8_t *rec;             // [nseq][cap_records][5]
     int32_t *count, *status;  // [nseq]
+    float *rho_scale;         // [nseq] the scale the records were made with, as the reference keeps it (rho_scale=scale: narrowed to float)
     int cap, np2cap, cap_records;
     em::WalkParams P;         // (scale is filled per sequence)
 };
@@ -162,6 +164,7 @@ __global__ __launch_bounds__(kEmWalkThreads) void k_em_walk(EmArgs a) {
     __shared__ uint32_t part[kEmWalkThreads];
     const int seq = blockIdx.x, tid = threadIdx.x;
     const int kn = max(0, min(a.kns[seq], a.cap));
+    if (tid == 0) a.rho_scale[seq] = (float)(a.scale ? a.scale[seq] : 1.0);   // edgemap_com.cpp:322
     if (kn <= 0) {
         if (tid == 0) a.count[seq] = 0;
         return;
@@ -255,6 +258,7 @@ struct edgehip_ctx::EdgeMapStore {
     std::vector<void *> dev;
     uint8_t *rec = nullptr;
     int32_t *count = nullptr, *status = nullptr;
+    float *rho_scale = nullptr;
     uint32_t *keys = nullptr, *offs = nullptr;
     unsigned long long *tmp = nullptr;
     KProfStage scale;                  // edgehip_edgemap_compress's scale on its way to the device
@@ -295,7 +299,7 @@ int edgehip_edgemap_enable(edgehip_ctx *c, int cap_records) {
     d->cap_records = cap_records;
     while ((size_t)d->np2cap < CAP) d->np2cap <<= 1;
     d->rec_bytes = (B * (size_t)cap_records * 5 + 15) & ~(size_t)15;
-    bool ok = em_alloc(d, &d->rec, d->rec_bytes) && em_alloc(d, &d->count, B) && em_alloc(d, &d->status, B) &&
+    bool ok = em_alloc(d, &d->rec, d->rec_bytes) && em_alloc(d, &d->count, B) && em_alloc(d, &d->status, B) && em_alloc(d, &d->rho_scale, B) &&
               em_alloc(d, &d->keys, B * (size_t)d->np2cap) && em_alloc(d, &d->offs, B * CAP) && em_alloc(d, &d->tmp, B * (size_t)cap_records) &&
               d->scale.create(B);
     for (hipEvent_t &e : d->ev_t) ok = ok && hipEventCreate(&e) == hipSuccess;
@@ -308,6 +312,8 @@ int edgehip_edgemap_enable(edgehip_ctx *c, int cap_records) {
     hipError_t z = hipMemsetAsync(d->rec, 0, d->rec_bytes, c->stream);
     if (z == hipSuccess) z = hipMemsetAsync(d->count, 0, sizeof(int32_t) * B, c->stream);
     if (z == hipSuccess) z = hipMemsetAsync(d->status, 0, sizeof(int32_t) * B, c->stream);
+    // an empty store reads as made with scale 1 (edgemap_com's constructor): the bit pattern of 1.0f, in-stream like the rest
+    if (z == hipSuccess) z = hipMemsetD32Async((hipDeviceptr_t)d->rho_scale, 0x3f800000, B, c->stream);
     if (z != hipSuccess) edgemap_free(c);
     EH_CHECK(z);
     return 0;
@@ -337,6 +343,7 @@ static int em_compress_enqueue(edgehip_ctx *c, int slot, const edgehip_edgemap_p
     a.kns = c->kn_slot + (size_t)slot * c->plan.nseq;
     a.scale = scale ? d->scale.dev : nullptr;
     a.keys = d->keys; a.offs = d->offs; a.tmp = d->tmp; a.rec = d->rec; a.count = d->count; a.status = d->status;
+    a.rho_scale = d->rho_scale;
     a.cap = c->plan.cap; a.np2cap = d->np2cap; a.cap_records = d->cap_records;
     a.P.min_line_len = p->min_line_len; a.P.max_line_len = p->max_line_len; a.P.match_n_t = p->match_n_t;
     a.P.max_cangle = std::cos(p->max_angle);
@@ -461,6 +468,34 @@ int edgehip_download_edgemap_batch(edgehip_ctx *c, int n, const int32_t *seqs, e
 
 int edgehip_download_edgemap(edgehip_ctx *c, int seq, edgehip_compressed_kl *records, int32_t *count, int32_t *status) {
     return edgehip_download_edgemap_batch(c, 1, &seq, &records, count, status);
+}
+
+bool edgehip::edgemap_store(edgehip_ctx *c, const uint8_t **records, const int32_t **counts, const float **rho_scale, int *cap_records) {
+    auto *d = c->edgemap;
+    if (!d) return false;
+    *records = d->rec; *counts = d->count; *rho_scale = d->rho_scale; *cap_records = d->cap_records;
+    return true;
+}
+
+int edgehip_upload_edgemap(edgehip_ctx *c, int seq, const edgehip_compressed_kl *records, int32_t count, float rho_scale) {
+    EH_ENTER(c);
+    auto *d = c->edgemap;
+    if (!d) { set_error("upload_edgemap: the record store is not enabled (edgehip_edgemap_enable)"); return EDGEHIP_ERR_STATE; }
+    if (seq < 0 || seq >= c->plan.nseq) { set_error("upload_edgemap: sequence out of range"); return EDGEHIP_ERR_ARG; }
+    if (count < 0 || count > d->cap_records || (count > 0 && !records)) { set_error("upload_edgemap: count outside [0, cap_records], or null records"); return EDGEHIP_ERR_ARG; }
+    // getPair divides rho by COMPRESSED_RHO_SCALING / rho_scale: that quotient has to be a finite positive float (rho_scale above
+    // about 5e-36), or every rho becomes +-0 and the walk's `kl1.rho < 0` no longer sees a closing record
+    if (!std::isfinite(rho_scale) || !(rho_scale > 0) || !std::isfinite(em::kSegRhoScaling / rho_scale)) {
+        set_error("upload_edgemap: rho_scale must be finite, > 0 and large enough that (32767 / 20) / rho_scale is a finite float");
+        return EDGEHIP_ERR_ARG;
+    }
+    const int32_t zero = 0;
+    if (count > 0) EH_CHECK(hipMemcpyAsync(d->rec + (size_t)seq * d->cap_records * 5, records, (size_t)count * 5, hipMemcpyHostToDevice, c->stream));
+    EH_CHECK(hipMemcpyAsync(d->count + seq, &count, sizeof count, hipMemcpyHostToDevice, c->stream));
+    EH_CHECK(hipMemcpyAsync(d->status + seq, &zero, sizeof zero, hipMemcpyHostToDevice, c->stream));
+    EH_CHECK(hipMemcpyAsync(d->rho_scale + seq, &rho_scale, sizeof rho_scale, hipMemcpyHostToDevice, c->stream));
+    EH_CHECK(hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 int edgehip_edgemap_device(edgehip_ctx *c, int first, int count, void *records_dev, void *counts_dev) {

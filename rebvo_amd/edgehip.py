@@ -35,6 +35,7 @@ NET_HEADER_DTYPE = np.dtype([("kline_num", "<i4"), ("km_num", "<i4"), ("k", "<f4
 # edgehip_compressed_kl = rebvo::compressed_kl (include/CommLib/edgemap_com.h:45-51), packed: 5 bytes
 COMPRESSED_KL_DTYPE = np.dtype({"names": ["x", "y", "rho", "s_rho"], "formats": ["u1", "u1", "<i2", "u1"], "offsets": [0, 1, 2, 4], "itemsize": 5})
 EDGEMAP_BAD_LINK, EDGEMAP_OVERFLOW, EDGEMAP_STEP_GUARD = 1, 2, 4   # status bits of edgehip_download_edgemap
+EDGEMAP_SEGMENT_OVERFLOW, EDGEMAP_ITEM_OVERFLOW = 1, 2             # status bits of edgehip_download_edgemap_segments
 # edgehip_ros_point / edgehip_ros_keyline: what the ROS nodelet builds per KeyLine (ros/src/rebvo_ros/src/rebvo_nodelet.cpp:176-212):
 # one xyz point of the cloud, one rebvo/Keyline.msg record (its little-endian wire body, packed: 52 bytes)
 ROS_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4")])
@@ -322,6 +323,8 @@ EXPORTS = [
     "edgehip_net_keylines_device", "edgehip_upload_net_keylines", "edgehip_depth_fill_net",
     "edgehip_edgemap_enable", "edgehip_edgemap_compress", "edgehip_download_edgemap", "edgehip_download_edgemap_batch",
     "edgehip_edgemap_device", "edgehip_edgemap_ms", "edgehip_edgemap_export", "edgehip_edgemap_export_fetch", "edgehip_edgemap_export_wait",
+    "edgehip_upload_edgemap", "edgehip_edgemap_decode_enable", "edgehip_edgemap_decode", "edgehip_download_edgemap_segments",
+    "edgehip_download_edgemap_segments_batch", "edgehip_edgemap_hide_visible", "edgehip_depth_fill_segments", "edgehip_edgemap_decode_ms",
     "edgehip_ros_enable", "edgehip_ros_pack", "edgehip_download_ros_edgemap", "edgehip_download_ros_edgemaps_batch",
     "edgehip_ros_edgemap_device", "edgehip_ros_edgemap_from_device", "edgehip_ros_export", "edgehip_ros_export_fetch", "edgehip_ros_export_wait",
     "edgehip_match_one_pass",
@@ -993,6 +996,76 @@ class EdgeHip:
         ms = (C.c_float * 4)()
         self._ck(self.lib.edgehip_edgemap_ms(self.ctx, ms))
         return tuple(ms)
+
+    # ---- the compressed edge map, received: segments, visibility, depth grid (edgemap_com_decoder) ----
+    def upload_edgemap(self, seq, records, rho_scale=1.0):
+        """edgehip_upload_edgemap: `records` (COMPRESSED_KL_DTYPE, or raw uint8 of shape (n, 5)) and their rho_scale become sequence
+        seq's stored edge map."""
+        rec = np.ascontiguousarray(records)
+        if rec.dtype != COMPRESSED_KL_DTYPE:
+            rec = np.ascontiguousarray(rec, np.uint8).reshape(-1, 5)
+        self._ck(self.lib.edgehip_upload_edgemap(self.ctx, int(seq), C.c_void_p(rec.ctypes.data if len(rec) else None), len(rec),
+                                                 C.c_float(rho_scale)))
+
+    def edgemap_decode_enable(self, cap_segments, cap_items=None):
+        """edgehip_edgemap_decode_enable: room for cap_segments segments and cap_items (segment, step) items per sequence.  cap_items
+        has no default (a sequence with more steps than cap_items folds nothing); cap_segments 0 (or None) frees the decoder."""
+        if cap_segments and cap_items is None:
+            raise ValueError("edgemap_decode_enable: cap_items is required (the steps of a sequence's segments, about their length in pixels)")
+        self._ck(self.lib.edgehip_edgemap_decode_enable(self.ctx, int(cap_segments or 0), int(cap_items or 0)))
+        self.edgemap_cap_segments = int(cap_segments or 0)   # the size of download_edgemap_segments' buffers: the library has no query for it
+
+    def edgemap_decode(self, x_scaling=0.0, y_scaling=0.0):
+        """edgehip_edgemap_decode: Decode on every sequence's stored records (in-stream)."""
+        self._ck(self.lib.edgehip_edgemap_decode(self.ctx, C.c_double(x_scaling), C.c_double(y_scaling)))
+
+    def download_edgemap_segments(self, seqs):
+        """edgehip_download_edgemap_segments(_batch): for a sequence -> (segments (n, 8) float32, flags (n,) uint8, status bits); for a
+        list of sequences -> a list of those, in its order."""
+        one = np.isscalar(seqs)
+        ids = np.ascontiguousarray([seqs] if one else seqs, np.int32)
+        cap = getattr(self, "edgemap_cap_segments", 0)
+        if not cap:
+            raise EdgeHipError("download_edgemap_segments: the decoder is not enabled through edgemap_decode_enable of this object")
+        n = len(ids)
+        segs = [np.zeros((cap, 8), np.float32) for _ in range(n)]
+        flags = [np.zeros(cap, np.uint8) for _ in range(n)]
+        ps = (C.c_void_p * n)(*[a.ctypes.data for a in segs])
+        pf = (C.c_void_p * n)(*[a.ctypes.data for a in flags])
+        counts, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._ck(self.lib.edgehip_download_edgemap_segments_batch(self.ctx, n, ids.ctypes.data_as(C.c_void_p), ps, pf,
+                                                                  C.c_void_p(counts.ctypes.data), C.c_void_p(status.ctypes.data)))
+        out = [(segs[j][:counts[j]].copy(), flags[j][:counts[j]].copy(), int(status[j])) for j in range(n)]
+        return out[0] if one else out
+
+    def edgemap_hide_visible(self, views):
+        """edgehip_edgemap_hide_visible: views[seq] is None (the sequence is left alone) or (DPose (3, 3), DPos (3,), k_em, k_new).
+        -> s_num per sequence (int32; -1 where left alone)."""
+        B = self.nseq
+        assert len(views) == B
+        keep, pr, pp = [], (C.c_void_p * B)(), (C.c_void_p * B)()
+        k_em, k_new = np.ones(B, np.float32), np.ones(B, np.float32)
+        for s, v in enumerate(views):
+            if v is None:
+                continue
+            r, p = np.ascontiguousarray(v[0], np.float64).reshape(9), np.ascontiguousarray(v[1], np.float64).reshape(3)
+            keep += [r, p]
+            pr[s], pp[s] = r.ctypes.data, p.ctypes.data
+            k_em[s], k_new[s] = v[2], v[3]
+        s_num = np.zeros(B, np.int32)
+        self._ck(self.lib.edgehip_edgemap_hide_visible(self.ctx, pr, pp, C.c_void_p(k_em.ctypes.data), C.c_void_p(k_new.ctypes.data),
+                                                       C.c_void_p(s_num.ctypes.data)))
+        return s_num
+
+    def depth_fill_segments(self, v_thresh, a_thresh_deg, use_visibility=False):
+        """edgehip_depth_fill_segments: the grids of every sequence from its decoded segments (fillDepthMap, in-stream)."""
+        self._ck(self.lib.edgehip_depth_fill_segments(self.ctx, C.c_double(v_thresh), C.c_double(a_thresh_deg), int(bool(use_visibility))))
+
+    def edgemap_decode_ms(self):
+        """edgehip_edgemap_decode_ms -> (decode_ms, hide_ms, items_ms, fill_ms) of the last such launches under profile_enable (-1: none)."""
+        ms = (C.c_float * 4)()
+        self._ck(self.lib.edgehip_edgemap_decode_ms(self.ctx, ms))
+        return tuple(float(v) for v in ms)
 
     def depth_fill_net(self, p_off=(0.0, 0.0)):
         """edgehip_depth_fill_net: the grids of every sequence from its stored wire records (in-stream)."""

@@ -6,6 +6,11 @@
 //   prepare_pkg              edgemap_com_sender::PreparePkg (:329-353): header with both CRC-16 fields + the records of one packet
 //   Receiver::check_recv_pak edgemap_com_receiver::CheckRecvPak (:374-429)
 //   get_pair / decode        edgemap_com::getPair (:46-86), edgemap_com_decoder::Decode (:431-440)
+//   update_pos               edgemap_com::UpdatePos (:142-160): DPose, DPos, DK of a stored map seen from a new view (the trigonometry of
+//                            the receiving side; the device takes its result)
+//   transform_pos / hide_visible   edgemap_com::TransformPos (:106-127), edgemap_com_decoder::HideVisible (:443-473)
+//   fill_depth_map           edgemap_com_decoder::fillDepthMap (:475-528) onto a plain grid, serially; what edgehip_depth_fill_segments is
+//                            tested against.  The per-segment and per-step rules are csrc/edgemap_seg.h, which the device runs too.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -15,6 +20,8 @@
 
 #include "edgehip.h"
 #include "edgemap_fit.h"
+#include "edgemap_seg.h"
+#include "linalg.h"
 
 namespace rebvo {
 namespace edgemap {
@@ -242,6 +249,144 @@ inline int decode(const compressed_kl *kls, int kl_num, float rho_scale, std::ve
         segs->push_back(s);
     }
     return (int)segs->size();
+}
+
+// Decode through the local rule of edgemap_seg.h (what k_em_decode runs): equal to decode() on every list
+inline int decode_local(const compressed_kl *kls, int kl_num, float rho_scale, std::vector<uncompressed_segment> *segs, int seg_max,
+                        double x_scaling = 0.5, double y_scaling = 1.0) {
+    segs->clear();
+    for (int i = 0; i < kl_num && (int)segs->size() < seg_max; i++) {
+        if (!seg_starts(i >= 1 ? kls[i - 1].rho : 0, kls[i].rho, i, kl_num)) continue;
+        SegPoint k0, k1;
+        seg_pair(kls[i].x, kls[i].y, kls[i].rho, kls[i].s_rho, kls[i + 1].x, kls[i + 1].y, kls[i + 1].rho, kls[i + 1].s_rho, rho_scale, x_scaling,
+                 y_scaling, &k0, &k1);
+        uncompressed_segment s;
+        s.k0 = {k0.x, k0.y, k0.rho, k0.s_rho};
+        s.k1 = {k1.x, k1.y, k1.rho, k1.s_rho};
+        s.visi_mask = true;
+        segs->push_back(s);
+    }
+    return (int)segs->size();
+}
+
+// ---- UpdatePos: the stored map (em_pos) seen from a new view (new_pos) ------------------------------------------------------------------
+struct PosDelta {
+    double DPose[9];   // Rn^T Ro, row-major
+    double DPos[3];    // Rn^T (Vo - Vn)
+    double DK;         // em_pos.K
+};
+// TooN::SO3<>::exp on the Vector<3, float> that makeVector(w[0], w[1], w[2]) makes of a nav package's floats (so3.h:203-285): theta_sq
+// and the mixed products w[i] * w[j] are float there, everything else double.  For float input this is what la::so3_exp restates for
+// double input; the branch structure is the same.
+inline la::Mat<3, 3> so3_exp_float(const float w[3]) {
+    const double one_6th = 1.0 / 6.0, one_20th = 1.0 / 20.0;
+    float dotf = 0;
+    for (int i = 0; i < 3; i++) dotf += w[i] * w[i];
+    const double theta_sq = dotf, theta = sqrt(theta_sq);
+    double A, B;
+    if (theta_sq < 1e-8) {
+        A = 1.0 - one_6th * theta_sq;
+        B = 0.5;
+    } else if (theta_sq < 1e-6) {
+        B = 0.5 - 0.25 * one_6th * theta_sq;
+        A = 1.0 - theta_sq * one_6th * (1.0 - one_20th * theta_sq);
+    } else {
+        const double inv_theta = 1.0 / theta;
+        A = sin(theta) * inv_theta;
+        B = (1 - cos(theta)) * (inv_theta * inv_theta);
+    }
+    la::Mat<3, 3> R;
+    const double wx2 = (double)w[0] * w[0], wy2 = (double)w[1] * w[1], wz2 = (double)w[2] * w[2];
+    R(0, 0) = 1.0 - B * (wy2 + wz2);
+    R(1, 1) = 1.0 - B * (wx2 + wz2);
+    R(2, 2) = 1.0 - B * (wx2 + wy2);
+    double a = A * w[2], b = B * (w[0] * w[1]);
+    R(0, 1) = b - a; R(1, 0) = b + a;
+    a = A * w[1]; b = B * (w[0] * w[2]);
+    R(0, 2) = b + a; R(2, 0) = b - a;
+    a = A * w[0]; b = B * (w[1] * w[2]);
+    R(1, 2) = b - a; R(2, 1) = b + a;
+    return R;
+}
+inline PosDelta update_pos(const em_compressed_nav_pkg &em_pos, const em_compressed_nav_pkg &new_pos) {
+    const la::Mat<3, 3> Rn = so3_exp_float(new_pos.w), Ro = so3_exp_float(em_pos.w);
+    const la::Mat<3, 3> RnT = la::transpose(Rn);
+    PosDelta d;
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) {
+            double s = 0;
+            for (int k = 0; k < 3; k++) s += RnT(r, k) * Ro(k, c);
+            d.DPose[3 * r + c] = s;
+        }
+        double s = 0;
+        for (int k = 0; k < 3; k++) s += RnT(r, k) * ((double)em_pos.p[k] - (double)new_pos.p[k]);
+        d.DPos[r] = s;
+    }
+    d.DK = em_pos.K;
+    return d;
+}
+
+struct Camera {        // what the decoder reads of cam_model: pp (float), zfm (double), sz
+    float ppx, ppy;
+    double zfm;
+    int w, h;
+    SegCam seg() const { SegCam c; c.ppx = ppx; c.ppy = ppy; c.zfm = zfm; c.w = (uint32_t)w; c.h = (uint32_t)h; return c; }
+};
+inline SegPoint as_point(const uncompressed_kl &k) { return SegPoint{k.x, k.y, k.rho, k.s_rho}; }
+
+inline uncompressed_kl transform_pos(const uncompressed_kl &p, const PosDelta &d, float k_em, float k_new, const Camera &cam) {
+    const SegPoint t = seg_transform_pos(as_point(p), d.DPose, d.DPos, k_em, k_new, cam.seg());
+    return uncompressed_kl{t.x, t.y, t.rho, t.s_rho};
+}
+// HideVisible with UpdatePos(pos) already applied (d): clears the flag of every visible segment the new view sees; a cleared flag
+// stays cleared.  Returns s_num: the segments that were visible and stay visible.
+inline int hide_visible(uncompressed_segment *segs, int seg_num, const PosDelta &d, float k_em, float k_new, const Camera &cam) {
+    int s_num = 0;
+    const SegCam c = cam.seg();
+    for (int i = 0; i < seg_num; i++) {
+        if (!segs[i].visi_mask) continue;
+        if (seg_seen(as_point(segs[i].k0), as_point(segs[i].k1), d.DPose, d.DPos, k_em, k_new, c)) segs[i].visi_mask = false;
+        else s_num++;
+    }
+    return s_num;
+}
+
+// ---- fillDepthMap onto a plain grid -----------------------------------------------------------------------------------------------------
+struct DepthGrid {     // depth_filler's cells: size = image size / block size, cell (x, y) at y * gw + x
+    int gw, gh, bw, bh;
+    std::vector<double> rho, s_rho, I_rho;
+    std::vector<uint8_t> fixed;
+    DepthGrid(int w, int h, int bw_, int bh_) : gw(w / bw_), gh(h / bh_), bw(bw_), bh(bh_) { reset(); }
+    void reset() {     // depth_filler::ResetData (depth_filler.cpp:41-56)
+        const size_t G = (size_t)(gw > 0 ? gw : 0) * (size_t)(gh > 0 ? gh : 0);
+        rho.assign(G, 1.0);
+        s_rho.assign(G, 40.0);
+        I_rho.assign(G, 1.0 / (40.0 * 40.0));
+        fixed.assign(G, 0);
+    }
+};
+// Every segment in list order, every step in step order, one update per step.  use_visibility: skip hidden segments (this library's
+// extension; the reference reads the records again and knows no flags).  gates[seg_num] (or null): the SegGate of every segment.
+// Returns the number of steps folded.
+inline long long fill_depth_map(const uncompressed_segment *segs, int seg_num, DepthGrid *g, const Camera &cam, double v_thresh, double a_thresh_deg,
+                                bool use_visibility = false, int *gates = nullptr) {
+    const double cos_a = cos(a_thresh_deg * M_PI / 180.0);
+    const SegCam c = cam.seg();
+    long long steps = 0;
+    for (int j = 0; j < seg_num; j++) {
+        int gate = -1;
+        if (!(use_visibility && !segs[j].visi_mask)) {
+            const SegSteps s = seg_steps(as_point(segs[j].k0), as_point(segs[j].k1), c, v_thresh, cos_a, &gate);
+            for (int i = 0; i < s.n; i++) {
+                const size_t cell = (size_t)seg_step_cell(s, i, g->bw, g->bh, g->gw, g->gh);
+                seg_fold(seg_step_rho(s, i), s.kl_I, &g->rho.at(cell), &g->s_rho.at(cell), &g->I_rho.at(cell));
+                g->fixed.at(cell) = 1;
+                steps++;
+            }
+        }
+        if (gates) gates[j] = gate;
+    }
+    return steps;
 }
 
 }  // namespace edgemap
