@@ -1065,6 +1065,53 @@ int edgehip_keyframe_covisibility_slot(edgehip_ctx *ctx, int slot, const edgehip
 /* Device time of the last of the two calls above, by HIP events: the field build (with the one read of the key frames) and the pair pass. */
 int edgehip_keyframe_covisibility_ms(edgehip_ctx *ctx, double *field_ms, double *pair_ms);
 
+/* ---- re-localisation against the key frames (kfvo::OptimizePosGT with kfvo::optimizeScale) ---------------------------------------
+ * The pose and scale of ring slot `slot`'s frame relative to every selected key frame of the same sequence — the positions of
+ * edgehip_keyframe_covisibility — for the whole batch in one call (src/mtracklib/kfvo.cpp:58-112, 222-260).  Per
+ * sequence and position t, with the query's (Pose, Pos, K) and key frame t's (Pose_t, Pos_t, K_t), KeyLines and field
+ * build_field(edges_t, field_radius, field_min_mod):
+ *     BRelRot = Pose_t.T() * Pose, BRelPos = Pose_t.T() * (Pos - Pos_t) / K, W0 = SO3<>(BRelRot).ln()           (:62-68)
+ *     Minimizer_RV_KF<double>(BRelPos, W0, ..., Kr = K / K_t, 5, 30 pi / 180, rho_tol, iter_max, rew_dis, s_rho_q, 0, X, RRV)   (:74)
+ *         — the arithmetic of edgehip_minimizer_rv_kf, run over the (sequence, position) pairs as its batch
+ *     mnum = #{m_id_f >= 0}                                                                                      (:76-82)
+ *     Kp = optimizeScale(kf_t, et, exp(W), BRelPos'): over the query KeyLines with m_id_f >= 0 and q1[2] > 0,
+ *          rTr0 += q1[2]^2 / v, rTr += q1[2] rho_b / v, v = s_rho^2 + s_rho_b^2; Kp = (rTr0 > 0 && rTr > 0) ? rTr0 / rTr : 1   (:222-260)
+ *     K = K_t * Kp, Pose = SO3<>(Pose_t) * exp(W), Pos = (SO3<>(Pose_t) * BRelPos') * K + Pos_t                  (:93-96)
+ * The two sums of optimizeScale are added in a fixed order of the device's own (per lane in KeyLine order with stride 256, then
+ * across lanes), not the reference's running sum: the same bits alone, in any batch and under any to_mask.  An empty query list
+ * returns score_ratio = 0, mnum = 0, Kp = 1, X = [BRelPos, W0], RRV = 0 (the reference leaves X and RRV unset there) and Pose / Pos
+ * from the unchanged W0 / BRelPos.  guard: query KeyLines whose transformed point q1 is not finite, plus one when Pose or Pose_t
+ * holds a NaN (broken preconditions, as with edgehip_kf_pair_count::guard).
+ * Read-only: no key frame, list entry or ring slot changes.  The reference writes the links into the query's m_id_f, where M pairs
+ * would overwrite each other; here every pair has its own link array, read by edgehip_keyframe_relocalize_links.
+ * Scratch is allocated by the first call and freed with the key frames.  Positions are served P = min(M, 8) at a time, so with
+ * T = ceil(w / 64) * ceil(h / 64) field tiles it is
+ *     nseq x P x (max_points x (72 + 4 T) B + ceil(w / 8) x ceil(h / 4) x 64 B + ceil(max_points / 256) x 256 B + 5.1 kB)
+ *   + nseq x M x (max_points x 4 B + 0.6 kB)                                  (the links and the results of every position)
+ * — the key frame's compact KeyLines 48 B, three residual buffers 24 B and the field's bins 4 T B per KeyLine of a pair; its index plane;
+ * carries and partial sums per block of 256 KeyLines; the minimiser's state.  752x480 (T = 96), 16 000 KeyLines: 7.4 MB per pair. */
+typedef struct edgehip_kf_reloc_args {
+    int32_t field_radius; float field_min_mod;   /* as edgehip_kf_covis_args; the radius is build_field's: 1 .. 255 */
+    int32_t iter_max; double rew_dis, rho_tol;
+} edgehip_kf_reloc_args;
+typedef struct edgehip_kf_reloc {
+    double X[6], RRV[36], score_ratio, F, F0, Kp, K, Pose[9], Pos[3];
+    int32_t mnum, evals, accepted, guard;
+} edgehip_kf_reloc;
+/* pose[nseq], or NULL for what edgehip_keyframe_insert takes by default; s_rho_q[nseq]; to_mask[nseq][M] (non-zero: serve the position),
+ * or NULL for all; out[nseq][M]; info[nseq] (may be NULL) as in edgehip_keyframe_covisibility_slot.  A position the sequence does not
+ * have, or that to_mask deselects, comes back with every integer field -1 (and zeros).  Synchronises.  EDGEHIP_ERR_STATE without
+ * key-frame tracking; EDGEHIP_ERR_ARG for NULL args, s_rho_q or out, a slot out of range, field_radius outside 1 .. 255, iter_max < 0
+ * or max_points > 65535; EDGEHIP_ERR_MEMORY when the scratch cannot be allocated: the context stays usable. */
+int edgehip_keyframe_relocalize(edgehip_ctx *ctx, int slot, const edgehip_kf_pose *pose, const double *s_rho_q, const uint8_t *to_mask,
+                                const edgehip_kf_reloc_args *args, edgehip_kf_reloc *out, edgehip_kf_list_info *info);
+/* The links of the last call's pair (seq, position): m_id_f[kn] (room for max_points; may be NULL), the query KeyLine's partner in key
+ * frame `position` or -1; kn_out = -1 (and nothing written) for a pair the last call did not serve.  Synchronises. */
+int edgehip_keyframe_relocalize_links(edgehip_ctx *ctx, int seq, int position, int32_t *m_id_f, int32_t *kn_out);
+/* Device time of the last edgehip_keyframe_relocalize, by HIP events: prepare (descriptors, the one read of the key frames, set-up,
+ * fields) and solve (the minimisation's launch chain, the count, the scale and the finish). */
+int edgehip_keyframe_relocalize_ms(edgehip_ctx *ctx, double *prepare_ms, double *solve_ms);
+
 /* ---- key-frame relative-pose constraint (kfvo::OptimizeRelContraint) ------------------------------------------------------------
  * The metric use of the links the tracking above maintains: from the key frame's m_id_f (direction 0) or the frame list's m_id_kf
  * (direction 1) alone, with no distance field, kfvo::OptimizeRelContraint (src/mtracklib/kfvo.cpp:527-604; its evaluation

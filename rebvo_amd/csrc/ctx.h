@@ -695,6 +695,31 @@ __device__ inline void frame_begin(SeqDev *sq, double t, double fps) {
 
 int quantile_enqueue(edgehip_ctx *c, int slot, double smin, double smax, double pct, int nbins, bool frame_begins = false, int retune_slot = -1);
 int build_field_enqueue(edgehip_ctx *c, int slot, int radius, float min_mod, bool clear_fwd = false);
+// The batch kfvo::Minimizer_RV_KF runs over: the context's own sequences, slot against slot (edgehip_minimizer_rv_kf), or keyframe_reloc.hip's
+// (sequence, key frame) pairs.  The kernels index every array below by the `seq` they are given, so a pair with arrays of its own looks like a
+// sequence to them.  Strides: cap (plan.cap), nblk (nblk_tvr), plan.f16stride; bins as build_field_enqueue lays them out.
+struct KfBatch {
+    int n;                          // entries ("sequences")
+    const KlSoA *kl_kf, *kl_cur;    // [n] the field's KeyLines (rec, rho, s_rho are read), the KeyLines that are evaluated (m_id_f is written)
+    const int32_t *kn_kf, *kn_cur;  // [n]
+    const float *retuned;           // [n] build_field's min_mod where the caller passes a negative one
+    int32_t *bin_cnt, *bins;        // [n][256], [n][tiles][cap]
+    uint16_t *field16;              // [n][f16stride]
+    int field_radius;               // the radius field16 was built with (the evaluation's max_r)
+    SeqDev *seq;                    // [n]
+    double *resid, *resid_carry, *partials, *block_last;   // [kResidBufs][n][cap], [kResidBufs][n][nblk], [n][nblk][kNumSums], [n][nblk]
+    uint32_t *framecount;           // [n], or null (neither the KF evaluation nor its steps read it)
+    const edgehip_kf_request *req;  // [n]
+    edgehip_kf_result *res;         // [n]
+    int f32;
+    bool fwd_key_in_tvr;            // the context's flag, for the context's own batch: TvrArgs::fwd_key as make_tvr_args sets it (not read with KF)
+};
+// build_field_enqueue's binned form over a KfBatch (kl_kf, kn_kf, retuned, bin_cnt, bins -> field16); EDGEHIP_ERR_ARG where build_field_enqueue refuses the
+// radius, EDGEHIP_ERR_STATE where the image has more tiles than the binned form serves
+int build_field_batch_enqueue(edgehip_ctx *c, const KfBatch &b, int radius, float min_mod);
+// the schedule of minimizer_kf_enqueue over a KfBatch: 2 (iter_max + 1) dependent launches and k_count_forward
+int minimizer_kf_batch_enqueue(edgehip_ctx *c, const KfBatch &b, double match_mod, double match_ang, double rho_tol, int iter_max,
+                               double reweight_distance, uint32_t match_num_thresh);
 int tvr_prepare_enqueue(edgehip_ctx *c, int slot_old, unsigned begin_ops = 0);   // begin_ops: LM ops of the step that opens a minimisation, run in the same launch
 int minimizer_enqueue(edgehip_ctx *c, int slot_new, int slot_old, int fc_index);
 int minimizer_v_enqueue(edgehip_ctx *c, int slot_new, int slot_old, int fc_index, int iter_max, double match_thresh,

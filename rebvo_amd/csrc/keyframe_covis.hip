@@ -54,12 +54,6 @@ constexpr uint32_t kCvIklMask = (1u << kCvIklBits) - 1;
 constexpr uint32_t kCvEmpty = 0xFFFFFFFFu;
 constexpr int kCvMaxRadius = 4094;   // (4095 << 20) | kCvIklMask would be kCvEmpty
 
-struct CvKf {                // a position of a sequence: kn < 0: the sequence has no key frame there
-    double Pose[9], Pos[3], K;
-    int32_t kn, src;         // src >= 0: list ring position; -1: the current key frame; -2: the ring slot of the query form
-};
-static_assert(sizeof(CvKf) == 112, "13 doubles + 2 ints");
-
 struct CvCompact {           // [nseq * (M + 1)][cap] each
     double *rho, *s_rho;
     float2 *p_m, *c_p, *u_m, *m_m;
@@ -85,35 +79,7 @@ __global__ void k_cv_desc(CvArgs a, const KfSeq *__restrict__ ks, KfListDev l, c
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= a.nseq * (a.M + 1)) return;
     const int seq = g / (a.M + 1), pos = g % (a.M + 1);
-    const int first = l.hdr ? l.ls[seq].first : 0, held = l.hdr ? max(0, min(l.ls[seq].held, l.capacity)) : 0;
-    CvKf d;
-    d.kn = -1; d.src = -1; d.K = 1.0;
-    for (int i = 0; i < 9; i++) d.Pose[i] = 0.0;
-    for (int i = 0; i < 3; i++) d.Pos[i] = 0.0;
-    const edgehip_kf_pose *p = nullptr;
-    if (pos < a.M && pos < held) {
-        const int at = (first + pos) % l.capacity;
-        const KfListHdr &h = l.hdr[(size_t)seq * l.capacity + at];
-        d.kn = max(0, min(h.kn, a.cap)); d.src = at;
-        p = &h.pose;
-    } else if (pos < a.M && pos == held && ks[seq].kf_count > 0) {
-        d.kn = max(0, min(ks[seq].kn, a.cap)); d.src = -1;
-        p = &ks[seq].pose;
-    } else if (pos == a.M && slot_kn) {
-        d.kn = max(0, min(slot_kn[seq], a.cap)); d.src = -2;
-        if (pose_in) p = &pose_in[seq];
-        else {   // what edgehip_keyframe_insert takes by default: the newest nav record's pose and seq_state's K
-            for (int i = 0; i < 9; i++) d.Pose[i] = nav[seq].Pose[i];
-            for (int i = 0; i < 3; i++) d.Pos[i] = nav[seq].Pos[i];
-            d.K = seqs[seq].pub.K;
-        }
-    }
-    if (p) {
-        for (int i = 0; i < 9; i++) d.Pose[i] = p->Pose[i];
-        for (int i = 0; i < 3; i++) d.Pos[i] = p->Pos[i];
-        d.K = p->K;
-    }
-    a.desc[g] = d;
+    a.desc[g] = kf_position(seq, pos, a.M, a.cap, ks, l, slot_kn, pose_in, seqs, nav);
 }
 
 // per (seq, to, from): kls_on_fov's BRelRot / BRelPos (kfvo.cpp:692-693), and the pair's counts start at 0, or are -1 for good

@@ -51,6 +51,49 @@ __device__ inline void kf_list_retire_head(const KfListDev &l, int seq, const Kf
     q.retire_pos = pos;
 }
 
+// ---- the positions of a sequence (keyframe_covis.hip, keyframe_reloc.hip) --------------------------------------------------------------
+// Position t of a sequence: its held list entries, oldest first, then its current key frame; position M (= list capacity + 1) is the ring
+// slot of the query forms.
+struct CvKf {                // a position of a sequence: kn < 0: the sequence has no key frame there
+    double Pose[9], Pos[3], K;
+    int32_t kn, src;         // src >= 0: list ring position; -1: the current key frame; -2: the ring slot of the query form
+};
+static_assert(sizeof(CvKf) == 112, "13 doubles + 2 ints");
+
+__device__ inline CvKf kf_position(const int seq, const int pos, const int M, const int cap, const KfSeq *__restrict__ ks, const KfListDev &l,
+                                   const int32_t *__restrict__ slot_kn, const edgehip_kf_pose *__restrict__ pose_in, const SeqDev *__restrict__ seqs,
+                                   const edgehip_nav *__restrict__ nav) {
+    const int first = l.hdr ? l.ls[seq].first : 0, held = l.hdr ? max(0, min(l.ls[seq].held, l.capacity)) : 0;
+    CvKf d;
+    d.kn = -1; d.src = -1; d.K = 1.0;
+    for (int i = 0; i < 9; i++) d.Pose[i] = 0.0;
+    for (int i = 0; i < 3; i++) d.Pos[i] = 0.0;
+    const edgehip_kf_pose *p = nullptr;
+    if (pos < M && pos < held) {
+        const int at = (first + pos) % l.capacity;
+        const KfListHdr &h = l.hdr[(size_t)seq * l.capacity + at];
+        d.kn = max(0, min(h.kn, cap)); d.src = at;
+        p = &h.pose;
+    } else if (pos < M && pos == held && ks[seq].kf_count > 0) {
+        d.kn = max(0, min(ks[seq].kn, cap)); d.src = -1;
+        p = &ks[seq].pose;
+    } else if (pos == M && slot_kn) {
+        d.kn = max(0, min(slot_kn[seq], cap)); d.src = -2;
+        if (pose_in) p = &pose_in[seq];
+        else {   // what edgehip_keyframe_insert takes by default: the newest nav record's pose and seq_state's K
+            for (int i = 0; i < 9; i++) d.Pose[i] = nav[seq].Pose[i];
+            for (int i = 0; i < 3; i++) d.Pos[i] = nav[seq].Pos[i];
+            d.K = seqs[seq].pub.K;
+        }
+    }
+    if (p) {
+        for (int i = 0; i < 9; i++) d.Pose[i] = p->Pose[i];
+        for (int i = 0; i < 3; i++) d.Pos[i] = p->Pos[i];
+        d.K = p->K;
+    }
+    return d;
+}
+
 }  // namespace edgehip
 
 struct edgehip_ctx::KfTrack {
@@ -82,6 +125,10 @@ struct edgehip_ctx::KfTrack {
     void *covis_arena = nullptr;
     int covis_m = 0;
     double covis_ms[2] = {0, 0};      // the last call's device time: field build (with the gather), pair pass
+    // keyframe_reloc.hip's scratch: allocated by the first edgehip_keyframe_relocalize, for reloc_m = list capacity + 1 positions per sequence
+    void *reloc_arena = nullptr;
+    int reloc_m = 0;
+    double reloc_ms[2] = {0, 0};      // the last call's device time: prepare (gather, set-up, fields), solve
     // keyframe_constraint.hip's scratch: the rows, allocated by the first edgehip_keyframe_constraint (92 B per KeyLine of capacity and sequence)
     void *kc_arena = nullptr;
     int32_t *kc_counts = nullptr;     // [nseq][2] edgehip_keyframe_mutual_exclusion's (links seen, links kept); allocated with the key frames
@@ -107,6 +154,7 @@ int kf_list_retire_one_enqueue(edgehip_ctx *c, int seq);
 // for a slot out of range, then the slot's KeyLines as edgehip_download_keylines returns them, ordered behind stage A.
 int kf_entry(edgehip_ctx *c, int slot, const char *who);
 void kf_covis_free(edgehip_ctx *c);                  // keyframe_covis.hip's scratch; behind a synchronisation of c->stream; no-op when absent
+void kf_reloc_free(edgehip_ctx *c);                  // keyframe_reloc.hip's scratch; the same
 void kf_constraint_free(edgehip_ctx *c);             // keyframe_constraint.hip's scratch; the same
 void kf_depth_free(edgehip_ctx *c);                  // keyframe_depth.hip's scratch; the same
 

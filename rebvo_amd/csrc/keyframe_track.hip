@@ -407,6 +407,7 @@ void edgehip::kf_track_free(edgehip_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     kf_list_free(c);
     kf_covis_free(c);
+    kf_reloc_free(c);
     kf_constraint_free(c);
     kf_depth_free(c);
     for (void *q : d->dev) (void)hipFree(q);

@@ -2676,6 +2676,36 @@ int quantile_enqueue(edgehip_ctx *c, int slot, double smin, double smax, double 
     return 0;
 }
 
+// The binned form's two launches over `nseq` KeyLine lists: the context's own (build_field_enqueue) or a KfBatch's (build_field_batch_enqueue).
+static void field_binned_launch(edgehip_ctx *c, int nseq, const KlSoA *kls, const int32_t *kns, const float *retuned, int32_t *bin_cnt, int32_t *bins,
+                                uint32_t *field, uint16_t *field16, int keep32, int radius, float min_mod, unsigned long long *fwd_key,
+                                int32_t *fwd_win) {
+    const DevicePlan &pl = c->plan;
+    const int ntx = (pl.w + FT - 1) / FT, nty = (pl.h + FT - 1) / FT;
+    // The bin entry carries the tile's t-range beside a 16-bit KeyLine id where both fit (every shipped configuration: search_range 40);
+    // otherwise it is the bare id and the rasteriser evaluates the range itself.  Both kernels of a launch take the same form.
+#ifndef EDGEHIP_FIELD_PACKED_RANGE
+#define EDGEHIP_FIELD_PACKED_RANGE 1
+#endif
+    const bool packed = EDGEHIP_FIELD_PACKED_RANGE && radius <= kPackedRadiusMax && pl.cap <= 65536;
+    auto bin = packed ? k_field_bin<true> : k_field_bin<false>;
+    auto raster = packed ? k_field_raster<true> : k_field_raster<false>;
+    hipLaunchKernelGGL(bin, dim3((pl.cap + 255) / 256, 1, nseq), dim3(256), 0, c->stream, kls, kns, retuned, bin_cnt, bins,
+                       pl.w, pl.h, radius, min_mod, ntx, nty, pl.cap, fwd_key, fwd_win);
+    hipLaunchKernelGGL(raster, dim3(ntx, nty, nseq), dim3(256), 0, c->stream, kls, bin_cnt, bins, field, field16, pl.f16stride, pl.f16tx,
+                       keep32, pl.w, pl.h, pl.fstride, pl.ftx, radius, ntx, pl.cap);
+}
+
+int build_field_batch_enqueue(edgehip_ctx *c, const KfBatch &b, int radius, float min_mod) {
+    ProfScope ps(c, PROF_B_FIELD);
+    const DevicePlan &pl = c->plan;
+    if (radius < 1 || radius > 255) { set_error("build_field: 1 <= radius <= 255"); return EDGEHIP_ERR_ARG; }
+    if (((pl.w + FT - 1) / FT) * ((pl.h + FT - 1) / FT) > kMaxTiles) { set_error("build_field: the image has more field tiles than the binned form serves"); return EDGEHIP_ERR_STATE; }
+    field_binned_launch(c, b.n, b.kl_kf, b.kn_kf, b.retuned, b.bin_cnt, b.bins, nullptr, b.field16, 0, radius, min_mod, nullptr, nullptr);
+    EH_LAUNCH_CHECK();
+    return 0;
+}
+
 int build_field_enqueue(edgehip_ctx *c, int slot, int radius, float min_mod, bool clear_fwd) {
     c->fwd_cleared = false;
     ProfScope ps(c, PROF_B_FIELD);
@@ -2684,21 +2714,10 @@ int build_field_enqueue(edgehip_ctx *c, int slot, int radius, float min_mod, boo
     c->field_radius = radius;
     const int ntx = (pl.w + FT - 1) / FT, nty = (pl.h + FT - 1) / FT;
     if (c->field_mode == 0 && ntx * nty <= kMaxTiles) {
-        // The bin entry carries the tile's t-range beside a 16-bit KeyLine id where both fit (every shipped configuration: search_range 40);
-        // otherwise it is the bare id and the rasteriser evaluates the range itself.  Both kernels of a launch take the same form.
-#ifndef EDGEHIP_FIELD_PACKED_RANGE
-#define EDGEHIP_FIELD_PACKED_RANGE 1
-#endif
-        const bool packed = EDGEHIP_FIELD_PACKED_RANGE && radius <= kPackedRadiusMax && pl.cap <= 65536;
-        auto bin = packed ? k_field_bin<true> : k_field_bin<false>;
-        auto raster = packed ? k_field_raster<true> : k_field_raster<false>;
-        hipLaunchKernelGGL(bin, dim3((pl.cap + 255) / 256, 1, pl.nseq), dim3(256), 0, c->stream, kldev(c, slot),
-                           c->kn_slot + (size_t)slot * pl.nseq, c->retuned_slot + (size_t)slot * pl.nseq, c->bin_cnt, c->bins,
-                           pl.w, pl.h, radius, min_mod, ntx, nty, pl.cap, clear_fwd ? c->fwd_key : nullptr, clear_fwd ? c->fwd_win : nullptr);
+        field_binned_launch(c, pl.nseq, kldev(c, slot), c->kn_slot + (size_t)slot * pl.nseq, c->retuned_slot + (size_t)slot * pl.nseq, c->bin_cnt,
+                            c->bins, c->field, c->field16, c->p.debug_planes ? 1 : 0, radius, min_mod, clear_fwd ? c->fwd_key : nullptr,
+                            clear_fwd ? c->fwd_win : nullptr);
         c->fwd_cleared = clear_fwd;
-        hipLaunchKernelGGL(raster, dim3(ntx, nty, pl.nseq), dim3(256), 0, c->stream, kldev(c, slot), c->bin_cnt,
-                           c->bins, c->field, c->field16, pl.f16stride, pl.f16tx, c->p.debug_planes ? 1 : 0, pl.w, pl.h,
-                           pl.fstride, pl.ftx, radius, ntx, pl.cap);
         c->field32_valid = c->p.debug_planes != 0;
         EH_LAUNCH_CHECK();
         return 0;
@@ -2876,41 +2895,88 @@ __global__ __launch_bounds__(256) void k_count_forward(const KlSoA *kls, const i
 
 // kfvo::Minimizer_RV_KF<double,false> (kfvo.cpp:1679-1825): the schedule is the reweighted Levenberg-Marquardt loop of
 // Minimizer_RV without an initialisation phase — every evaluation with ReWeight and ProcJF, Cholesky solves throughout.
-int minimizer_kf_enqueue(edgehip_ctx *c, int slot_kf, int slot_cur, double match_mod, double match_ang, double rho_tol, int iter_max,
-                         double reweight_distance, uint32_t match_num_thresh) {
+int minimizer_kf_batch_enqueue(edgehip_ctx *c, const KfBatch &b, double match_mod, double match_ang, double rho_tol, int iter_max,
+                               double reweight_distance, uint32_t match_num_thresh) {
+    const DevicePlan &pl = c->plan;
     int e;
-    c->fc_index = slot_kf;   // not read by the KF evaluation, not written by LM_FINISH_KF
 #define EH_TRY(x) if ((e = (x)) != 0) return e
-    EH_TRY(rec_refresh_enqueue(c, slot_kf));   // a key frame has been the old slot of a later frame: its gradients were turned
-    EH_TRY(tvr_prepare_enqueue(c, slot_cur));
+    {
+        ProfScope ps(c, PROF_B_PREP);
+        hipLaunchKernelGGL(k_tvr_prepare, dim3((pl.cap + 255) / 256, 1, b.n), dim3(256), 0, c->stream, b.kl_cur, b.kn_cur, c->P0, b.resid, b.resid_carry,
+                           b.seq, pl.cap, c->nblk_tvr, pl.zfm);
+        EH_LAUNCH_CHECK();
+    }
     auto eval = [&](bool last) -> int {
-        TvrArgs a = make_tvr_args(c, slot_kf, slot_cur, 0.0, reweight_distance, match_num_thresh, last ? 1 : 0);
-        a.kf = c->kf_req_dev; a.kf_match_mod = match_mod; a.kf_match_cang = cos(match_ang); a.kf_rho_tol = rho_tol;
+        TvrArgs a;
+        a.kl_old = b.kl_cur; a.kl_new = b.kl_kf; a.kn_old = b.kn_cur;
+        a.field16 = b.field16; a.f16stride = pl.f16stride; a.f16tx = pl.f16tx; a.P0 = c->P0; a.resid = b.resid; a.resid_carry = b.resid_carry;
+        a.block_last = b.block_last; a.partials = b.partials; a.seq = b.seq;
+        a.block_last_z = b.block_last + (size_t)b.n * c->nblk_tvr;      // (the zero-init chain's: no KF evaluation touches them)
+        a.partials_z = b.partials + (size_t)b.n * c->nblk_tvr * kNumSums;
+        a.framecount = b.framecount;
+        a.w = pl.w; a.h = pl.h; a.cap = pl.cap; a.nblk = c->nblk_tvr; a.nseq = b.n;
+        a.zfm = pl.zfm; a.inv_zfm = 1.0 / pl.zfm; a.max_r = (double)b.field_radius; a.match_thresh = 0.0; a.k_huber = reweight_distance;
+        a.inv_k_huber = 1.0 / reweight_distance;
+        a.ppx = pl.ppx; a.ppy = pl.ppy; a.match_num_thresh = match_num_thresh; a.write_mid = last ? 1 : 0;
+        a.fwd_key = (a.write_mid && b.fwd_key_in_tvr) ? c->fwd_key : nullptr;   // (as make_tvr_args sets it; the KF evaluation does not read it)
+        a.kf = b.req; a.kf_match_mod = match_mod; a.kf_match_cang = cos(match_ang); a.kf_rho_tol = rho_tol;
         a.use_grec = 0;
         ProfScope ps(c, PROF_B_TRYVELROT);
-        hipLaunchKernelGGL(k_try_velrot_kf, dim3(c->nblk_tvr, 1, c->plan.nseq), dim3(kTvrThreads), 0, c->stream, a);
+        hipLaunchKernelGGL(k_try_velrot_kf, dim3(c->nblk_tvr, 1, b.n), dim3(kTvrThreads), 0, c->stream, a);
+        EH_LAUNCH_CHECK();
+        return 0;
+    };
+    auto step = [&](unsigned ops) -> int {
+        ProfScope ps(c, PROF_B_LMSTEP);
+        LmArgs a;
+        a.seq = b.seq; a.partials = b.partials; a.block_last = b.block_last; a.resid_carry = b.resid_carry;
+        a.block_last_z = b.block_last + (size_t)b.n * c->nblk_tvr;
+        a.partials_z = b.partials + (size_t)b.n * c->nblk_tvr * kNumSums;
+        a.framecount = b.framecount;
+        a.nblk = c->nblk_tvr; a.nseq = b.n; a.ops = ops; a.init_type = c->p.tracker_init_type;
+        a.kf_in = b.req; a.kf_out = b.res;
+        a.f32 = b.f32;
+        hipLaunchKernelGGL(k_lm_step, dim3(b.n), dim3(64), 0, c->stream, a);
         EH_LAUNCH_CHECK();
         return 0;
     };
     const int M = iter_max;
-    EH_TRY(launch_lm(c, slot_kf, LM_BEGIN_KF | LM_SETUP_X | LM_PHASE_BC));
+    EH_TRY(step(LM_BEGIN_KF | LM_SETUP_X | LM_PHASE_BC));
     EH_TRY(eval(M <= 0));
     {
         unsigned ops = LM_REDUCE_CUR | LM_INIT | LM_RESET_V;
         if (M > 0) ops |= LM_SOLVE_CHOL | LM_SETUP_XNEW; else ops |= LM_FINISH_KF;
-        EH_TRY(launch_lm(c, slot_kf, ops));
+        EH_TRY(step(ops));
     }
     for (int it = 0; it < M; it++) {
         EH_TRY(eval(it == M - 1));
         unsigned ops = LM_REDUCE_NEW | LM_GAIN_RATIO | LM_SWAP_ON_ACCEPT;
         if (it < M - 1) ops |= LM_SOLVE_CHOL | LM_SETUP_XNEW; else ops |= LM_FINISH_KF;
-        EH_TRY(launch_lm(c, slot_kf, ops));
+        EH_TRY(step(ops));
     }
-    hipLaunchKernelGGL(k_count_forward, dim3(c->plan.nseq), dim3(256), 0, c->stream, kldev(c, slot_cur),
-                       c->kn_slot + (size_t)slot_cur * c->plan.nseq, c->kf_res_dev);
+    hipLaunchKernelGGL(k_count_forward, dim3(b.n), dim3(256), 0, c->stream, b.kl_cur, b.kn_cur, b.res);
     EH_LAUNCH_CHECK();
 #undef EH_TRY
     return 0;
+}
+
+// the context's own sequences, slot against slot: the field of slot_kf is the context's (build_field_enqueue built it)
+int minimizer_kf_enqueue(edgehip_ctx *c, int slot_kf, int slot_cur, double match_mod, double match_ang, double rho_tol, int iter_max,
+                         double reweight_distance, uint32_t match_num_thresh) {
+    c->fc_index = slot_kf;   // not read by the KF evaluation, not written by LM_FINISH_KF
+    if (int e = rec_refresh_enqueue(c, slot_kf)) return e;   // a key frame has been the old slot of a later frame: its gradients were turned
+    const size_t B = c->plan.nseq;
+    KfBatch b = {};
+    b.n = (int)B;
+    b.kl_kf = kldev(c, slot_kf); b.kl_cur = kldev(c, slot_cur);
+    b.kn_kf = c->kn_slot + (size_t)slot_kf * B; b.kn_cur = c->kn_slot + (size_t)slot_cur * B;
+    b.field16 = c->field16; b.field_radius = c->field_radius; b.seq = c->seq;
+    b.resid = c->resid; b.resid_carry = c->resid_carry; b.partials = c->partials; b.block_last = c->block_last;
+    b.framecount = c->framecount + (size_t)c->fc_index * B;
+    b.req = c->kf_req_dev; b.res = c->kf_res_dev;
+    b.f32 = c->tracker_f32 ? 1 : 0;
+    b.fwd_key_in_tvr = c->fwd_key_in_tvr;
+    return minimizer_kf_batch_enqueue(c, b, match_mod, match_ang, rho_tol, iter_max, reweight_distance, match_num_thresh);
 }
 
 // Minimizer_RV<double,false>: the static evaluation/step schedule of global_tracker.cpp:631-816

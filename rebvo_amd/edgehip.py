@@ -261,6 +261,24 @@ KF_PAIR_COUNT_DTYPE = np.dtype(KfPairCount)
 assert KF_PAIR_COUNT_DTYPE.itemsize == 16 and C.sizeof(KfCovisArgs) == 24
 
 
+class KfRelocArgs(C.Structure):
+    """edgehip_kf_reloc_args: build_field's (radius, min_mod) and OptimizePosGT's (iter_max, rew_dis, rho_tol)."""
+    _fields_ = [("field_radius", C.c_int32), ("field_min_mod", C.c_float), ("iter_max", C.c_int32), ("rew_dis", C.c_double),
+                ("rho_tol", C.c_double)]
+
+
+class KfReloc(C.Structure):
+    """edgehip_kf_reloc: Minimizer_RV_KF's X, RRV, F / F0, optimizeScale's Kp, OptimizePosGT's K, Pose, Pos, the links counted, the
+    evaluations run, steps accepted and the guard count."""
+    _fields_ = [("X", C.c_double * 6), ("RRV", C.c_double * 36), ("score_ratio", C.c_double), ("F", C.c_double), ("F0", C.c_double),
+                ("Kp", C.c_double), ("K", C.c_double), ("Pose", C.c_double * 9), ("Pos", C.c_double * 3),
+                ("mnum", C.c_int32), ("evals", C.c_int32), ("accepted", C.c_int32), ("guard", C.c_int32)]
+
+
+KF_RELOC_DTYPE = np.dtype(KfReloc)
+assert KF_RELOC_DTYPE.itemsize == 488 and C.sizeof(KfRelocArgs) == 32
+
+
 class KfConstraintArgs(C.Structure):
     """edgehip_kf_constraint_args: OptimizeRelContraint's etracket_2_keyframe, iter_max and k_huber."""
     _fields_ = [("direction", C.c_int32), ("iter_max", C.c_int32), ("k_huber", C.c_double)]
@@ -333,6 +351,7 @@ EXPORTS = [
     "edgehip_keyframe_set_save", "edgehip_keyframe_list_enable", "edgehip_keyframe_list_info", "edgehip_download_keyframe_list",
     "edgehip_download_keyframe_list_batch", "edgehip_keyframe_list_restore",
     "edgehip_keyframe_covisibility", "edgehip_keyframe_covisibility_slot", "edgehip_keyframe_covisibility_ms",
+    "edgehip_keyframe_relocalize", "edgehip_keyframe_relocalize_links", "edgehip_keyframe_relocalize_ms",
     "edgehip_keyframe_constraint", "edgehip_keyframe_mutual_exclusion", "edgehip_keyframe_constraint_ms",
     "edgehip_keyframe_map_depth", "edgehip_keyframe_translate_depth", "edgehip_keyframe_list_translate_depth", "edgehip_keyframe_depth_ms",
     "edgehip_keyframe_depth_select",
@@ -1454,6 +1473,38 @@ class EdgeHip:
         """-> (field build ms, pair pass ms) of the last covisibility call, by HIP events."""
         f, p = C.c_double(0), C.c_double(0)
         self._ck(self.lib.edgehip_keyframe_covisibility_ms(self.ctx, C.byref(f), C.byref(p)))
+        return f.value, p.value
+
+    # ---- re-localisation against the key frames (kfvo::OptimizePosGT, optimizeScale) ----
+    def keyframe_relocalize(self, slot, s_rho_q, field_radius, iter_max, rew_dis, rho_tol, field_min_mod=0.0, poses=None, to_mask=None):
+        """Ring slot `slot`'s frame (poses: one KfPose per sequence, or None for the newest nav record and seq_state.K; s_rho_q: a
+        scalar or one per sequence) against every key frame of the same sequence that to_mask (nseq, M) selects (None: all) ->
+        (results (nseq, M) of KF_RELOC_DTYPE, info).  A position the sequence lacks or the mask deselects has every integer field -1."""
+        m = getattr(self, "_kf_list_capacity", 0) + 1
+        out = np.zeros((self.nseq, m), KF_RELOC_DTYPE)
+        info = np.zeros(self.nseq, KF_LIST_INFO_DTYPE)
+        a = KfRelocArgs(int(field_radius), float(field_min_mod), int(iter_max), float(rew_dis), float(rho_tol))
+        q = np.ascontiguousarray(np.broadcast_to(np.asarray(s_rho_q, np.float64), (self.nseq,))).copy()
+        arr = None if poses is None else (KfPose * self.nseq)(*poses)
+        mk = None
+        if to_mask is not None:
+            mk = np.ascontiguousarray(np.broadcast_to(np.asarray(to_mask).astype(np.uint8), (self.nseq, m))).copy()
+        self._ck(self.lib.edgehip_keyframe_relocalize(self.ctx, int(slot), arr, q.ctypes.data_as(C.c_void_p),
+                                                      None if mk is None else mk.ctypes.data_as(C.c_void_p), C.byref(a),
+                                                      out.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p)))
+        return out, info
+
+    def keyframe_relocalize_links(self, seq, position):
+        """-> m_id_f [kn] int32 of the last keyframe_relocalize call's pair (seq, position), or None for a pair it did not serve."""
+        m = np.full(self.cap, -1, np.int32)
+        kn = C.c_int32(-1)
+        self._ck(self.lib.edgehip_keyframe_relocalize_links(self.ctx, int(seq), int(position), m.ctypes.data_as(C.c_void_p), C.byref(kn)))
+        return None if kn.value < 0 else m[:kn.value].copy()
+
+    def keyframe_relocalize_ms(self):
+        """-> (prepare ms, solve ms) of the last keyframe_relocalize call, by HIP events."""
+        f, p = C.c_double(0), C.c_double(0)
+        self._ck(self.lib.edgehip_keyframe_relocalize_ms(self.ctx, C.byref(f), C.byref(p)))
         return f.value, p.value
 
     # ---- key-frame relative-pose constraint (kfvo::OptimizeRelContraint, mutualExclusionSimple) ----

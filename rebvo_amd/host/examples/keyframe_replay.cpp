@@ -3,7 +3,7 @@
 // REBVO::kf_list goes into a key-frame file the reference's kf_visualizer loads.  Used by tests/test_keyframe_host_gpu.py.
 //
 //   keyframe_replay <GlobalConfig> <frames.rgb24> <objects> <frames_per_object> <t0> <dt> <out_prefix>
-//                   [--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis] [--constraint] [--depth]
+//                   [--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis] [--constraint] [--depth] [--relocalize [N]]
 //
 // frames.rgb24 = objects x frames_per_object x ImageHeight x ImageWidth x 3 bytes: object i's frame k is frame i * frames_per_object + k
 // and carries the stamp t0 + k dt.  --group puts all objects into one batch group of that name (without it every object has its own
@@ -18,6 +18,11 @@
 // --constraint: at the same point, REBVO::keyframeConstraint of every object in both directions with (iter_max, k_huber) = (10, 2): the
 // current key frame against the newest frame.  Prints "constraint <i> dir <d>:" and X[6], ratio, E, E0, Kp, W_Kp with 17 significant
 // digits, then links, inliers, evals, accepted, guard.
+// --relocalize [N]: REBVO::keyframeRelocalize of every object against all its positions with (SearchRange, 0, iter_max 5, rew_dis 2,
+// rho_tol 3): the newest frame against every key frame the device holds.  With N, after every N-th frame but the first (the objects are then
+// stepped frame by frame, as with --depth): "relocalize <i> frame <k> position <t>: <mnum> <score_ratio> <Kp>" for every position the
+// object has.  Before CleanUp(), at the same point as --covis: "relocalize <i> position <t>:" and mnum, evals, accepted, guard, then
+// score_ratio, Kp, K, X[6], Pose[9], Pos[3] with 17 significant digits, for all positions.
 // --depth: REBVO::keyframeMapDepth of every object with (ReshapeQAbsolute, ReshapeQRelative, LocationUncertainty) = (1e-3, 5e-2, 2) after
 // every frame but the first (the objects are then stepped frame by frame: each frame's record is waited for).  Prints "mapdepth <i> frame <k>: <count>";
 // before CleanUp(), REBVO::keyframeTranslateDepth (0, optim_scale) and then (1, false) of every object: "translate <i> dir <d>:" and
@@ -87,7 +92,7 @@ static int map_views(const REBVOParameters &prm, std::vector<keyframe> &list) {
 int main(int argn, char **argv) {
     if (argn < 8) {
         std::cout << "usage: keyframe_replay <GlobalConfig> <frames.rgb24> <objects> <frames_per_object> <t0> <dt> <out_prefix> "
-                     "[--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis] [--constraint] [--depth]\n";
+                     "[--group NAME] [--start F] [--end F] [--disagree] [--map] [--covis] [--constraint] [--depth] [--relocalize [N]]\n";
         return 2;
     }
     const int N = atoi(argv[3]), K = atoi(argv[4]);
@@ -95,7 +100,8 @@ int main(int argn, char **argv) {
     const std::string prefix = argv[7];
     std::string group;
     int start = -1, end = -1;
-    bool disagree = false, map = false, covis = false, constraint = false, depth = false;
+    bool disagree = false, map = false, covis = false, constraint = false, depth = false, relocalize = false;
+    int reloc_every = 0;
     for (int a = 8; a < argn; a++) {
         const std::string s = argv[a];
         if (s == "--group" && a + 1 < argn) group = argv[++a];
@@ -106,6 +112,10 @@ int main(int argn, char **argv) {
         else if (s == "--covis") covis = true;
         else if (s == "--constraint") constraint = true;
         else if (s == "--depth") depth = true;
+        else if (s == "--relocalize") {
+            relocalize = true;
+            if (a + 1 < argn && argv[a + 1][0] >= '0' && argv[a + 1][0] <= '9') reloc_every = atoi(argv[++a]);
+        }
         else { std::cout << "unknown argument " << s << "\n"; return 2; }
     }
     if (N < 1 || K < 2) { std::cout << "bad counts\n"; return 2; }
@@ -154,9 +164,23 @@ int main(int argn, char **argv) {
             (*ptr).copyFrom(reinterpret_cast<const RGB24Pixel *>(pool.data() + fb * ((size_t)i * K + k)));
             obj[i]->releaseCustomCamBuffer();
         }
-        if (!depth || k == 0) continue;   // (the first frame has no record and no key frame)
+        const bool reloc_now = reloc_every > 0 && k % reloc_every == 0;
+        if ((!depth && !reloc_now) || k == 0) continue;   // (the first frame has no record and no key frame)
         wait_for(t0 + dt * k);
-        for (int i = 0; i < N && !bad; i++) {
+        for (int i = 0; i < N && reloc_now && !bad; i++) {
+            KfRelocArgs ra;
+            ra.field_radius = (int)prm.SearchRange; ra.field_min_mod = 0.f; ra.iter_max = 5; ra.rew_dis = 2.0; ra.rho_tol = 3.0;
+            std::vector<KfReloc> rows;
+            int m = 0;
+            if (!obj[i]->keyframeRelocalize(ra, nullptr, rows, m)) { std::cout << "relocalize " << i << " frame " << k << ": refused\n"; continue; }
+            for (int t = 0; t < m; t++) {
+                if (rows[(size_t)t].mnum < 0) continue;
+                char buf[96];
+                snprintf(buf, sizeof buf, " %.17g %.17g", rows[(size_t)t].score_ratio, rows[(size_t)t].Kp);
+                std::cout << "relocalize " << i << " frame " << k << " position " << t << ": " << rows[(size_t)t].mnum << buf << "\n";
+            }
+        }
+        for (int i = 0; i < N && depth && !bad; i++) {
             int count = 0;
             if (!obj[i]->keyframeMapDepth(1e-3, 5e-2, 2.0, count)) { std::cout << "mapdepth " << i << " frame " << k << ": refused\n"; continue; }
             std::cout << "mapdepth " << i << " frame " << k << ": " << count << "\n";
@@ -188,6 +212,22 @@ int main(int argn, char **argv) {
             for (double x : v) { snprintf(buf, sizeof buf, " %.17g", x); std::cout << buf; }
             std::cout << " " << kc.links << " " << kc.inliers << " " << kc.evals << " " << kc.accepted << " " << kc.guard << "\n";
         }
+    for (int i = 0; i < N && relocalize && !bad; i++) {
+        KfRelocArgs ra;
+        ra.field_radius = (int)prm.SearchRange; ra.field_min_mod = 0.f; ra.iter_max = 5; ra.rew_dis = 2.0; ra.rho_tol = 3.0;
+        std::vector<KfReloc> rows;
+        int m = 0;
+        if (!obj[i]->keyframeRelocalize(ra, nullptr, rows, m)) { std::cout << "relocalize " << i << ": refused\n"; continue; }
+        for (int t = 0; t < m; t++) {
+            const KfReloc &r = rows[(size_t)t];
+            char buf[64];
+            std::cout << "relocalize " << i << " position " << t << ": " << r.mnum << " " << r.evals << " " << r.accepted << " " << r.guard;
+            std::vector<double> v = {r.score_ratio, r.Kp, r.K};
+            v.insert(v.end(), r.X, r.X + 6); v.insert(v.end(), r.Pose, r.Pose + 9); v.insert(v.end(), r.Pos, r.Pos + 3);
+            for (double x : v) { snprintf(buf, sizeof buf, " %.17g", x); std::cout << buf; }
+            std::cout << "\n";
+        }
+    }
     for (int i = 0; i < N && depth && !bad; i++)
         for (int d = 0; d < 2; d++) {
             KfDepth kd;

@@ -80,6 +80,14 @@ struct KfConstraint {
     double ratio, E, E0, Kp, W_Kp;
     int32_t links, inliers, evals, accepted, guard, pad;
 };
+// (mirror only) REBVO::keyframeRelocalize's arguments and result: edgehip_kf_reloc_args / edgehip_kf_reloc of include/edgehip.h, field for
+// field — build_field's (radius, min_mod) and kfvo::OptimizePosGT's iter_max, rew_dis, rho_tol; Minimizer_RV_KF's X, RRV, F / F0, F, F0,
+// optimizeScale's Kp, the K, Pose, Pos OptimizePosGT returns, the links counted, the evaluations run, the steps accepted and the guard count.
+struct KfRelocArgs { int32_t field_radius; float field_min_mod; int32_t iter_max; double rew_dis, rho_tol; };
+struct KfReloc {
+    double X[6], RRV[36], score_ratio, F, F0, Kp, K, Pose[9], Pos[3];
+    int32_t mnum, evals, accepted, guard;
+};
 // (mirror only) REBVO::keyframeTranslateDepth's result: edgehip_kf_depth of include/edgehip.h, field for field — the links used, the guard
 // bits, the key frame's K the rewrite used and optimizeScaleBack's two sums.
 struct KfDepth { int32_t count, guard; double K, rTr, rTr0; };
@@ -597,6 +605,15 @@ public:
     // the newest nav record's Pose and Pos with the running scale K (what a key frame taken from that frame would carry).  Served by
     // the group's thread between two steps, as keyframeCovisibility is; false under the same conditions.
     bool keyframeConstraint(const KfConstraintArgs &args, KfConstraint &out);
+    // (mirror only) Where this object's newest frame is relative to its key frames: kfvo::OptimizePosGT with kfvo::optimizeScale
+    // (src/mtracklib/kfvo.cpp:58-112, 222-260) against every key frame the device holds for it — the positions of keyframeCovisibility —
+    // on the device (edgehip_keyframe_relocalize, include/edgehip.h), for an object on the group engine with TrackKeyFrames = 1 between
+    // Init() and CleanUp().  The query is the newest slot with the newest nav record's pose and the running K; s_rho_q is the value the
+    // frame driver last used for this object.  positions: m flags (non-zero: serve the position), or null for all; out[m], every integer
+    // field -1 for a position the object does not have or the flags deselect.  Only this object's pairs are solved, whatever the other
+    // members of the group hold.  Served by the group's thread between two steps, as keyframeCovisibility is; false under the same
+    // conditions, and when positions has another size than m.
+    bool keyframeRelocalize(const KfRelocArgs &args, const std::vector<uint8_t> *positions, std::vector<KfReloc> &out, int &m);
     // (mirror only) Depth along the links between this object's current key frame and its newest frame, on the device
     // (edgehip_keyframe_map_depth / edgehip_keyframe_translate_depth, include/edgehip.h), for an object on the group engine with
     // TrackKeyFrames = 1 between Init() and CleanUp(); the frame is the newest slot, its pose the newest nav record's with the running K,

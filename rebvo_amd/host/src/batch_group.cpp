@@ -210,6 +210,10 @@ public:
     static_assert(sizeof(KfDepth) == sizeof(edgehip_kf_depth), "the mirror's struct is the C ABI's");
     struct DepthReq { int seat = -1; bool map = false; double q[3] = {0, 0, 0}; int direction = 0, optim_scale = 0; KfDepth *out = nullptr; bool done = false, ok = false; };
     std::vector<DepthReq *> depth_reqs;
+    // REBVO::keyframeRelocalize: the same queue; positions: the member's flags per position, or null for all
+    static_assert(sizeof(KfRelocArgs) == sizeof(edgehip_kf_reloc_args) && sizeof(KfReloc) == sizeof(edgehip_kf_reloc), "the mirror's structs are the C ABI's");
+    struct RelocReq { int seat = -1; edgehip_kf_reloc_args args; const std::vector<uint8_t> *positions = nullptr; std::vector<KfReloc> *out = nullptr; int *m = nullptr; bool done = false, ok = false; };
+    std::vector<RelocReq *> reloc_reqs;
     std::atomic<int> covis_waiting{0};
     bool thread_done = false;
     void serveCovis();
@@ -712,8 +716,10 @@ void REBVO::BatchGroup::serveCovis() {
     std::vector<CovisReq *> take;
     std::vector<ConstraintReq *> take_kc;
     std::vector<DepthReq *> take_kd;
+    std::vector<RelocReq *> take_rl;
     {
         std::lock_guard<std::mutex> lk(mut);
+        take_rl.swap(reloc_reqs);
         take.swap(covis_reqs);
         take_kc.swap(constraint_reqs);
         take_kd.swap(depth_reqs);
@@ -757,6 +763,33 @@ void REBVO::BatchGroup::serveCovis() {
         }
     }
     const size_t M = kKfListCapacity + 1;
+    if (!take_rl.empty()) {   // the newest frame (its nav record's pose, the running K: the call's defaults) against the member's key frames
+        std::vector<edgehip_kf_reloc> all_rl((size_t)cap * M);
+        std::vector<uint8_t> to((size_t)cap * M);
+        std::vector<double> q((size_t)cap, 0.0);
+        bool have = kf_track;
+        for (int i = 0; i < cap && have; i++) {
+            edgehip_seq_state st;
+            have = edgehip_get_state(hip, i, &st) == 0;
+            q[(size_t)i] = st.s_rho_q;
+        }
+        for (RelocReq *r : take_rl) {
+            bool ok = have && (!r->positions || r->positions->size() == M);
+            if (ok) {
+                std::fill(to.begin(), to.end(), (uint8_t)0);
+                for (size_t t = 0; t < M; t++) to[(size_t)r->seat * M + t] = r->positions ? (*r->positions)[t] : (uint8_t)1;
+                ok = edgehip_keyframe_relocalize(hip, edgehip_cur_slot(hip), nullptr, q.data(), to.data(), &r->args, all_rl.data(), nullptr) == 0;
+            }
+            if (ok) {
+                r->out->resize(M);
+                std::memcpy(r->out->data(), all_rl.data() + (size_t)r->seat * M, sizeof(KfReloc) * M);
+                *r->m = (int)M;
+            }
+            std::lock_guard<std::mutex> lk(mut);
+            r->ok = ok;
+            r->done = true;
+        }
+    }
     std::vector<edgehip_kf_pair_count> all((size_t)cap * M * M);
     for (CovisReq *r : take) {
         const bool ok = kf_track && edgehip_keyframe_covisibility(hip, &r->args, all.data(), nullptr) == 0;
@@ -782,6 +815,8 @@ void REBVO::BatchGroup::refuseCovis() {
         constraint_reqs.clear();
         for (DepthReq *r : depth_reqs) r->done = true;
         depth_reqs.clear();
+        for (RelocReq *r : reloc_reqs) r->done = true;
+        reloc_reqs.clear();
     }
     cv.notify_all();
 }
@@ -809,6 +844,20 @@ bool REBVO::keyframeConstraint(const KfConstraintArgs &args, KfConstraint &out) 
     std::unique_lock<std::mutex> lk(g->mut);
     if (!g->started || g->thread_done || g->failed || !g->kf_track || !g->seats[group_seat].running) return false;
     g->constraint_reqs.push_back(&r);
+    g->covis_waiting.store(1, std::memory_order_release);
+    g->cv.wait(lk, [&] { return r.done; });
+    return r.ok;
+}
+
+bool REBVO::keyframeRelocalize(const KfRelocArgs &args, const std::vector<uint8_t> *positions, std::vector<KfReloc> &out, int &m) {
+    BatchGroup *g = group;
+    if (!g || group_seat < 0 || quit) return false;
+    BatchGroup::RelocReq r;
+    r.seat = group_seat; r.positions = positions; r.out = &out; r.m = &m;
+    std::memcpy(&r.args, &args, sizeof r.args);
+    std::unique_lock<std::mutex> lk(g->mut);
+    if (!g->started || g->thread_done || g->failed || !g->kf_track || !g->seats[group_seat].running) return false;
+    g->reloc_reqs.push_back(&r);
     g->covis_waiting.store(1, std::memory_order_release);
     g->cv.wait(lk, [&] { return r.done; });
     return r.ok;
